@@ -32,10 +32,25 @@ under a launcher (WORLD_SIZE set, which must equal N).  One process per GPU,
 RCCL (`nccl` backend) only for barriers and the max-time / checksum
 reductions; no data-path collective (but for the opt-in --c4-scatter).
 
-Also reported: per-kernel HIP-event times (in-library, stamped by each kernel's dispatch),
-the roofline of the dominant kernel, erasure decode (configs[3]), the
-host-memory pipeline (PCIe-inclusive), single-codeword call latency, and the
-reference CPU path timed on the host cores (rank 0, N=1 only).
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, runs W warm-up
+and K timed steps, checks that every timed step restored its codewords and
+prints the result line (`value`, `ms_per_step`).  One corrupted copy per step is
+kept when they all fit in half the free memory; a longer run times its steps in
+segments of as many copies as fit and refills them between the segments,
+untimed, so a step is the same work for every K.
+
+--dump-outputs DIR: after the timed steps, what the last of them returned to
+its caller goes to DIR/<name>.npy (dump_outputs; a fixed, seeded sample of the
+rows plus whole-batch checksums).  The inputs depend only on the arguments, so
+two builds can be compared file by file.
+
+--full: everything else, after the timed steps of the plain run -- per-kernel
+HIP-event times (in-library, stamped by each kernel's dispatch) from a second
+loop of the same steps, the roofline of the dominant kernel, the mixed channel,
+erasure decode (configs[3]), the host-memory pipeline (PCIe-inclusive),
+single-codeword call latency, general-parameter codes, configs[4] (and
+--c4-scatter), the parity sample against the reference CPU path, and that path
+timed on the host cores (rank 0, N=1 only).
 
 --backend MODULE replaces the GPU codec by MODULE.Backend (tests only: the
 gloo launcher test runs the same launcher, partition and reduction code on
@@ -75,8 +90,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--overlap", type=int, default=0,
                     help="1: each step's encode on a second stream, concurrent with its decode")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the bench measures and checks (module "
+                         "docstring); the --no-* and --c4-* options select among those parts")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed to DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--batch", type=int, default=1 << 20, help="codewords per GPU (weak-scaling line)")
     ap.add_argument("--c4-total", type=int, default=1 << 26, help="configs[4]: codewords split over all ranks")
     ap.add_argument("--c4-chunk", type=int, default=1 << 24, help="configs[4]: codewords per rank-chunk (memory)")
@@ -523,9 +543,16 @@ def run_weak(be, ranks, args, rank, world):
     be.sync()
     clean = be.like(cw)
     be.copy(clean, cw)
-    ncopy = args.warmup + 2 * args.steps  # two timed loops (plain, then with kernel events)
     nenc = max(1, args.enc_copies)
-    copies = be.kind != "gpu" or (ncopy + nenc) * B * N <= 0.5 * be.free_bytes()
+    # one corrupted copy per step (warm-up and timed), made before the timed
+    # loop, where they fit in half the free memory; else as many as fit, and
+    # the steps run in segments of that many with the copies refilled between
+    # the segments, untimed.  Not even one: the channel runs in place, timed.
+    npool = args.warmup + args.steps
+    if be.kind == "gpu":
+        npool = min(npool, int(0.5 * be.free_bytes() // (B * N)) - nenc)
+    npool = max(0, -int(ranks.max(-npool)))  # the same segments on every rank
+    copies = npool > 0
     # the timed encode rotates over nenc message buffers (same messages), so
     # no step re-encodes a buffer the Infinity Cache still holds
     enc = [cw]
@@ -534,67 +561,114 @@ def run_weak(be, ranks, args, rank, world):
             b = be.like(cw)
             be.copy(b, clean)
             enc.append(b)
-    bad = []
-    if copies:  # one corrupted copy per step, made before the timed loop
-        for _ in range(ncopy):
-            b = be.like(cw)
+    bad = [be.like(cw) for _ in range(npool)]
+    pool = {"next": 0, "end": 0}  # bad[next:end] are corrupted and not yet decoded
+
+    def refill(n):
+        for b in bad[:n]:
             be.copy(b, clean)
             be.channel(b, err)
-            bad.append(b)
         be.sync()
+        pool["next"], pool["end"] = 0, n
 
-    def step(k):
+    refill(npool)
+    state = {"nbad": 0, "last": cw}
+
+    def step(k, j):
         # the step's encode (messages in cw) and decode (a corrupted copy)
         # share no buffer: with --overlap the encode goes to a second stream
         be.encode(enc[k % len(enc)], side=args.overlap and copies and be.kind == "gpu")
         if copies:
-            d = bad[k]
+            d = bad[j]
         else:
             be.channel(cw, err)
             d = cw
         be.decode(d, st)
+        return d
 
-    for k in range(args.warmup):
-        step(k)
+    def loop(k0, nsteps, check=True):
+        """steps k0 .. k0 + nsteps - 1; the time between the barriers around
+        each segment of steps, summed, max over ranks"""
+        done, total = 0, 0.0
+        while done < nsteps:
+            if copies and pool["next"] == pool["end"]:
+                refill(min(npool, nsteps - done))
+            seg = min(nsteps - done, pool["end"] - pool["next"]) if copies else nsteps - done
+            j0 = pool["next"]
+            ranks.barrier(be.sync)
+            t0 = time.perf_counter()
+            for j in range(seg):
+                state["last"] = step(k0 + done + j, j0 + j)
+            ranks.barrier(be.sync)
+            total += time.perf_counter() - t0
+            pool["next"] += seg
+            if check:  # every timed step restored its codewords
+                state["nbad"] += sum(be.n_diff(b, clean) for b in (bad[j0:j0 + seg] if copies else [cw]))
+            done += seg
+        return ranks.max(total)
+
+    loop(0, args.warmup, check=False)
     # timed loop 1 (`value`): the codec kernels only
-    ranks.barrier(be.sync)
-    t0 = time.perf_counter()
-    for k in range(args.steps):
-        step(args.warmup + k)
-    ranks.barrier(be.sync)
-    elapsed = ranks.max(time.perf_counter() - t0)
-    # timed loop 2: the same steps on fresh copies with HIP events on every
-    # launch (poporon_amd_timing: hipExtLaunchKernel stamps them at the
-    # kernel's own start and end, so they agree with a rocprofv3 kernel trace)
-    # -- per-kernel times and the roofline; the events cost ~5 % of a step,
-    # so they stay out of loop 1
-    kt = None
-    elapsed_ev = None
-    if be.kind == "gpu" and copies:
-        be.rs.timing(True)
-        ranks.barrier(be.sync)
-        t1 = time.perf_counter()
-        for k in range(args.steps):
-            step(args.warmup + args.steps + k)
-        ranks.barrier(be.sync)
-        elapsed_ev = ranks.max(time.perf_counter() - t1)
-        kt = {k: be.rs.timing_read(k) for k in be.P.KERNEL_NAMES}
-        be.rs.timing(False)
-    nbad = be.n_bad(st, 16) + sum(be.n_diff(b, clean) for b in enc)
-    timed = bad[args.warmup:args.warmup + (2 if elapsed_ev else 1) * args.steps] if copies else [cw]
-    nbad += sum(be.n_diff(b, clean) for b in timed)
-    # parity sample: every SAMPLE_STRIDE-th codeword's timed
-    # encode and decode, checked against the reference after the timed loops
-    idx = sample_index(B)
-    rows = be.host(clean, idx)
-    samples = {"encode": {"msg": rows[:, :K], "got_par": rows[:, K:], "first": first},
-               "decode16": {"in": channel_rows(rows, be.host(err[0], idx), be.host(err[1], idx)),
-                            "out": be.host(timed[-1], idx), "ok": be.host(st[0], idx), "cor": be.host(st[1], idx),
-                            "first": first}}
+    elapsed = loop(args.warmup, args.steps)
+    nbad = be.n_bad(st, 16)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, be, rank, world, first, enc[(args.warmup + args.steps - 1) % len(enc)],
+                     state["last"], st)
+    kt, elapsed_ev, samples = None, None, {}
+    if args.full:
+        # timed loop 2: the same steps on fresh copies with HIP events on every
+        # launch (poporon_amd_timing: hipExtLaunchKernel stamps them at the
+        # kernel's own start and end, so they agree with a rocprofv3 kernel trace)
+        # -- per-kernel times and the roofline; the events cost ~5 % of a step,
+        # so they stay out of loop 1
+        if be.kind == "gpu" and copies:
+            be.rs.timing(True)
+            elapsed_ev = loop(args.warmup + args.steps, args.steps)
+            kt = {k: be.rs.timing_read(k) for k in be.P.KERNEL_NAMES}
+            be.rs.timing(False)
+            nbad += be.n_bad(st, 16)
+        # parity sample (SURVEY 8(d)): every SAMPLE_STRIDE-th codeword's timed
+        # encode and decode, checked against the reference after the timed loops
+        idx = sample_index(B)
+        rows = be.host(clean, idx)
+        samples = {"encode": {"msg": rows[:, :K], "got_par": rows[:, K:], "first": first},
+                   "decode16": {"in": channel_rows(rows, be.host(err[0], idx), be.host(err[1], idx)),
+                                "out": be.host(state["last"], idx), "ok": be.host(st[0], idx),
+                                "cor": be.host(st[1], idx), "first": first}}
+    nbad += state["nbad"] + sum(be.n_diff(b, clean) for b in enc)
     csum = be.checksum(cw, first)
     del bad, enc
     return {"elapsed": elapsed, "elapsed_ev": elapsed_ev, "kt": kt, "nbad": ranks.sum_int(nbad), "copies": copies,
             "checksum": ranks.sum_u64(csum), "cw": cw, "clean": clean, "err": err, "st": st, "samples": samples}
+
+
+DUMP_ROWS = 16384  # sampled codewords of --dump-outputs: 16384 x (32 + 255) floats, 19 MB
+
+
+def dump_outputs(out_dir, be, rank, world, first, encoded, decoded, st):
+    """--dump-outputs: what the last timed step handed back to its caller --
+    the parity bytes its encode wrote, and the codewords, ok flags and
+    corrected counts its decode left -- for a fixed, seeded sample of
+    DUMP_ROWS codewords of the batch (`rows.npy`: their indices), as float32
+    arrays <name>.npy (<name>_rankR.npy on rank R > 0); `totals.npy` (float64)
+    covers the whole batch: the position-weighted checksums of the encoded
+    and the decoded buffer as (high, low) 32-bit halves, the codewords with
+    ok = 1 and those not (ok = 1, corrected = 16)."""
+    import numpy as np
+    B = encoded.shape[0]
+    idx = np.sort(np.random.default_rng(SEED + 100).choice(B, size=min(B, DUMP_ROWS), replace=False)).astype(np.int64)
+    ce, cd = be.checksum(encoded, first), be.checksum(decoded, first)
+    out = {"rows": (idx + first).astype(np.float64),
+           "encode_parity": be.host(encoded, idx)[:, K:].astype(np.float32),
+           "decode_codewords": be.host(decoded, idx).astype(np.float32),
+           "decode_ok": be.host(st[0], idx).astype(np.float32),
+           "decode_corrected": be.host(st[1], idx).astype(np.float32),
+           "totals": np.array([ce >> 32, ce & 0xFFFFFFFF, cd >> 32, cd & 0xFFFFFFFF, be.count_ok(st), be.n_bad(st, 16)],
+                              np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"_rank{rank}" if rank else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), a)
 
 
 def run_erasure(be, ranks, args, rank, world, w, ne=32, nerr=0):
@@ -1309,8 +1383,9 @@ def main(argv=None):
         "dtype": "u8",
         "data": "synthetic (counter-hash messages, 16 random-magnitude errors at unique positions per codeword)",
         "config": {"workload": "RS(255,223) round trip: encode + decode with 16 errors per codeword, "
-                               f"{B} codewords per GPU (BASELINE configs[1]+[2]); configs[4] (the "
-                               f"{args.c4_total}-codeword strong split) under 'configs4'",
+                               f"{B} codewords per GPU (BASELINE configs[1]+[2])"
+                               + (f"; configs[4] (the {args.c4_total}-codeword strong split) under 'configs4'"
+                                  if args.full and not args.no_c4 else ""),
                    "codewords_per_gpu": B, "layout": "255-byte codeword rows, stride 255",
                    "code": "poporon_config_rs_default (8, 0x11D, fcr 1, prim 1, 32 roots)"},
         # one bandwidth definition everywhere: 255 B per codeword
@@ -1318,10 +1393,11 @@ def main(argv=None):
         "GB_per_s": round(value * 2 * CW_BYTES / 1e9, 2),
         "hbm_frac_of_peak": round(value * 2 * CW_BYTES / 1e9 / (HBM_PEAK_GBS * world), 4),
         "bytes_per_unit": "510 = 255 (encode: 223 read + 32 written) + 255 (decode: 255 read) per round trip",
-        "step": f"encode {B} messages + decode {B} corrupted codewords (16 errors each); the test channel corrupts "
-                "one copy per step before the timed loops; `value` / `ms_per_step` from a loop without per-kernel "
-                "events, per-kernel times and the roofline from a second loop of the same steps with HIP events "
-                "stamped by every kernel's dispatch (`ms_per_step_instrumented`)" if w["copies"]
+        "step": (f"encode {B} messages + decode {B} corrupted codewords (16 errors each); the test channel corrupts "
+                 "one copy per step outside the timed loops; `value` / `ms_per_step` from a loop without per-kernel "
+                 "events" + ("" if not args.full else
+                             ", per-kernel times and the roofline from a second loop of the same steps with HIP "
+                             "events stamped by every kernel's dispatch (`ms_per_step_instrumented`)")) if w["copies"]
                 else "encode + channel (in place) + decode",
         "verified": w["nbad"] == 0,
         "weak_checksum": w["checksum"],
@@ -1329,7 +1405,8 @@ def main(argv=None):
     if one_device() and not args.backend:
         line["rehearsal"] = f"POPORON_BENCH_ONE_DEVICE: all {world} ranks on cuda:0, gloo reductions; not a scaling number"
     samples = dict(w.pop("samples"))
-    if not args.no_mixed:
+    full = args.full  # everything below but the printed line
+    if full and not args.no_mixed:
         mix = run_mixed(be, ranks, args, rank, world, w)
         samples["decode_mixed"] = mix.pop("_sample")
         line["decode_mixed"] = mix
@@ -1421,22 +1498,23 @@ def main(argv=None):
             line["decode_mixed"].pop("_kt", None)
             line["decode_mixed"].pop("_steps", None)
     del w
-    if not args.no_c4:
+    if full and not args.no_c4:
         c4 = run_strong(be, ranks, args, rank, world)
         samples.update(c4.pop("_samples"))
         line["configs4"] = c4
         line["parity_checksum"] = c4["parity_checksum"]
         line["verified"] = line["verified"] and c4["verified"]
-    if args.c4_scatter and world > 1:
+    if full and args.c4_scatter and world > 1:
         sc = run_scatter(be, ranks, args, rank, world)
         line["configs4_scatter"] = sc
         line["verified"] = line["verified"] and sc["verified"]
     # every sampled codeword of every mode against the reference CPU path
     # (after all timed loops)
-    ps = parity_sample(samples, ranks)
-    line["parity_sample"] = ps
-    line["verified"] = line["verified"] and all(v["mismatches"] == 0 for k, v in ps.items() if isinstance(v, dict))
-    if gpu and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full:
+        ps = parity_sample(samples, ranks)
+        line["parity_sample"] = ps
+        line["verified"] = line["verified"] and all(v["mismatches"] == 0 for v in ps.values() if isinstance(v, dict))
+    if full and gpu and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline()
         lat = line.get("single_call_latency")
         if lat:  # the drop-in path against the reference on one host core, same box and run

@@ -30,7 +30,7 @@ def _run(gpus, extra=(), env_extra=None):
     env.update(env_extra or {})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--backend", "tests.bench_cpu_backend",
            "--batch", "256", "--steps", "1", "--warmup", "0", "--c4-total", "1000", "--c4-chunk", "300",
-           "--c4-reps", "1", *extra]
+           "--c4-reps", "1", "--full", *extra]
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
 
 
@@ -63,6 +63,48 @@ def test_launcher_ranks_and_checksum():
     msgs2 = T.synth_rows_cpu(bench.SEED, 0, 512, 223)
     cw2 = np.concatenate([msgs2, Oracle().encode_batch(msgs2)], 1)
     assert T.checksum_cpu(cw2, 0) == two["weak_checksum"]
+
+
+def _plain(capsys, monkeypatch, *extra):
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    bench.main(["--gpus", "1", "--backend", "tests.bench_cpu_backend", "--batch", "300", "--steps", "3", "--warmup", "1",
+                *extra])
+    lines = [x for x in capsys.readouterr().out.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path, capsys, monkeypatch):
+    """Without --full the line holds the headline only; --dump-outputs writes
+    the last timed step's outputs as float .npy files, identical from run to
+    run and equal to the oracle's."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    line = _plain(capsys, monkeypatch, "--dump-outputs", str(a))
+    assert line["verified"] and line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "codewords/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - 300 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]
+    for k in ("configs4", "decode_mixed", "parity_sample", "cpu_baseline", "kernels", "roofline", "general_params"):
+        assert k not in line
+    _plain(capsys, monkeypatch, "--dump-outputs", str(b), "--steps", "2")
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["decode_codewords.npy", "decode_corrected.npy", "decode_ok.npy", "encode_parity.npy", "rows.npy",
+                     "totals.npy"]
+    got = {n[:-4]: np.load(a / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    for n in names:
+        assert np.array_equal(got[n[:-4]], np.load(b / n)), n
+    from oracle import Oracle
+    msgs = T.synth_rows_cpu(bench.SEED, 0, 300, 223)
+    rows = got["rows"].astype(np.int64)
+    assert (rows == np.arange(300)).all()  # a batch below the sample size is dumped whole
+    cw = np.concatenate([msgs, Oracle().encode_batch(msgs)], 1)
+    assert (got["encode_parity"] == cw[rows, 223:]).all() and (got["decode_codewords"] == cw[rows]).all()
+    assert (got["decode_ok"] == 1).all() and (got["decode_corrected"] == 16).all()
+    cs = T.checksum_cpu(cw, 0)
+    assert got["totals"].tolist() == [cs >> 32, cs & 0xFFFFFFFF, cs >> 32, cs & 0xFFFFFFFF, 300, 0]
 
 
 def test_gpus_must_match_world_size():

@@ -5,7 +5,7 @@
 # time limit.  Output: gpurun_out/bsz_N.json (the bench line).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 mkdir -p gpurun_out
-F="--no-c4 --no-cpu-baseline --no-host --no-latency --no-mixed --no-erasure"
+F="--full --no-c4 --no-cpu-baseline --no-host --no-latency --no-mixed --no-erasure"
 sizes=${*:-1048576 524288 262144}
 for b in $sizes; do
     timeout -k 10 200 python bench.py --batch "$b" $F > "gpurun_out/bsz_$b.json" 2> "gpurun_out/bsz_$b.err" || exit 3

@@ -3,7 +3,7 @@
 
     python tools/exp_bench.py build/a.so build/b.so ...
 
-Runs `bench.py --no-cpu-baseline --no-host --no-c4 --no-latency --steps 6`
+Runs `bench.py --full --no-cpu-baseline --no-host --no-c4 --no-latency --steps 6`
 with POPORON_AMD_LIB pointing at each build and prints the kernel averages of
 the decode16, erasure32 and errata16e8 lines."""
 import json
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 for lib in sys.argv[1:]:
     env = dict(os.environ, POPORON_AMD_LIB=os.path.abspath(lib))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-host", "--no-c4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-host", "--no-c4",
                         "--no-latency", "--no-mixed", "--no-general", "--steps", "6"], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     line = [x for x in r.stdout.splitlines() if x.startswith("{")]
     if not line:

@@ -25,7 +25,7 @@ for step in "$@"; do
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) run tests 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     tests_all) run tests_all 900 python -m pytest tests -m gpu -q ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     beside) # the cross-handle batch / single-call test on each build in build/*.so, then the tree's
         for so in build/*.so; do
             POPORON_AMD_LIB=$so run "beside_$(basename $so .so)" 300 python -u -m pytest tests/test_gpu_fullsize.py \
@@ -54,7 +54,7 @@ for step in "$@"; do
     ab) # A/B of the experiment builds in build/*.so, alternated twice (same box)
         run ab 900 python tools/exp_bench.py $(ls build/*.so) $(ls build/*.so) ;;
     prof) run prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- \
-        python3 bench.py --no-cpu-baseline --no-host --no-c4 --no-latency --no-mixed --no-general --steps 10 ;;
+        python3 bench.py --full --no-cpu-baseline --no-host --no-c4 --no-latency --no-mixed --no-general --steps 10 ;;
     gwtests) run gw_tests 400 python -u -m pytest tests/test_gpu_generic_wave.py -x -q --timeout 120 --timeout-method thread ;;
     glat) run glat_wave 300 python tools/general_lat.py --calls 30 --path wave
           run glat_lane 300 python tools/general_lat.py --calls 30 --path lane ;;
