@@ -136,7 +136,11 @@ bool poporon_decode_batch(poporon_t *pprn, uint8_t *data, size_t data_stride, ui
  * 0 = encode LFSR, 1 = remainder LFSR, 2 = correction (single kernel),
  * 3 = check LFSR; the split error-mode decode of large batches: 4 = BM +
  * Omega, 5 = Chien, 6 = Forney, 8 = apply, 7 = the one-codeword-per-wave
- * decoder over the codewords the split kernels hand on.  Erasure-mode
+ * decoder over the codewords the split kernels hand on (for batches routed
+ * by their size Forney and the apply are one launch, charged to 8, and 6
+ * records none; they are two launches, 6 and 8, under
+ * POPORON_AMD_DECODE_PATH=split, and POPORON_AMD_DECODE_TAIL=fused / split in
+ * the environment at poporon_create chooses either way).  Erasure-mode
  * batches of that size: 1, 9 = the 32-sorted-erasure kernel (prim 1), 4 / 5
  * / 6 = the errata kernels, 7 = the same per-wave decoder over the rest, 8 =
  * apply.  A batch of one codeword: 10 = the one-workgroup decoder

@@ -182,6 +182,9 @@ struct _poporon_t {
     bool fast;      /* served by the RS(255,223) kernels (rs_kernels.hip, rs_correct.hip) */
     int decode_path; /* 0: by batch size, 1: split kernels (rs_fast.hip), 2: single kernel (rs_correct_k),
                       * 3: one codeword per wave (rs_wave_k) */
+    int decode_tail; /* split kernels: 0 Forney and apply in one kernel (rs_forney_apply_k), 1 rs_forney_k then
+                      * rs_apply_k; POPORON_AMD_DECODE_TAIL=fused|split, default: fused where the batch size
+                      * chooses the path, every stage its own kernel under POPORON_AMD_DECODE_PATH=split */
     bool generic;   /* served by the general-parameter kernels (rs_generic.hip) */
     bool lfsr_nr;   /* generic code, num_roots <= 32: batch encodes on the LFSR kernel (rsk_encode_nr) */
     bool nrsplit;   /* ... and large error-mode batches decode on the split kernels (params_nrsplit) */
@@ -554,6 +557,8 @@ static void build_decode_tables(poporon_t *h, uint32_t nr)
     p.force_verify = (fv && fv[0] == '1') ? 1u : 0u;
     const char *dp = getenv("POPORON_AMD_DECODE_PATH");
     h->decode_path = !dp ? 0 : !strcmp(dp, "split") ? 1 : !strcmp(dp, "single") ? 2 : !strcmp(dp, "wave") ? 3 : 0;
+    const char *dt = getenv("POPORON_AMD_DECODE_TAIL");
+    h->decode_tail = dt && !strcmp(dt, "split") ? 1 : dt && !strcmp(dt, "fused") ? 0 : h->decode_path == 1 ? 1 : 0;
 }
 
 /* General-parameter kernels: byte symbols (2 <= m <= 8) and 1 <= num_roots
@@ -1487,18 +1492,25 @@ static bool launch_split(poporon_t *h, const RsCorrParams &prm, const RsSplitWs 
         HIP_OK(rsk_chien(g.tab, &prm, &ws, count, ok, corrected, g.num_cu, s));
         t.done();
     }
-    {
-        KernelTimer t(g, POPORON_AMD_KERNEL_FORNEY, s);
-        HIP_OK(rsk_forney(g.tab, &prm, &ws, d_data, ds, d_par, ps, count, ok, corrected, g.num_cu, s));
-        t.done();
-    }
-    {
+    if (h->decode_tail == 0) {
+        /* Forney and the block apply in one kernel (rs_forney_apply_k), charged to the apply's id */
         KernelTimer t(g, POPORON_AMD_KERNEL_APPLY, s);
-        if (nr)
-            HIP_OK(rsk_apply_nr(&prm, &ws, d_data, ds, d_par, ps, count, npar, s));
-        else
-            HIP_OK(rsk_apply(&prm, &ws, d_data, ds, d_par, ps, count, s));
+        HIP_OK(rsk_forney_apply(g.tab, &prm, &ws, d_data, ds, d_par, ps, count, npar, ok, corrected, g.num_cu, s));
         t.done();
+    } else {
+        {
+            KernelTimer t(g, POPORON_AMD_KERNEL_FORNEY, s);
+            HIP_OK(rsk_forney(g.tab, &prm, &ws, d_data, ds, d_par, ps, count, ok, corrected, g.num_cu, s));
+            t.done();
+        }
+        {
+            KernelTimer t(g, POPORON_AMD_KERNEL_APPLY, s);
+            if (nr)
+                HIP_OK(rsk_apply_nr(&prm, &ws, d_data, ds, d_par, ps, count, npar, s));
+            else
+                HIP_OK(rsk_apply(&prm, &ws, d_data, ds, d_par, ps, count, s));
+            t.done();
+        }
     }
     {
         /* what the split kernels hand on: one codeword per wave (rs_wave_k) */

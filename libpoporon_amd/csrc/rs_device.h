@@ -291,6 +291,8 @@ hipError_t rsk_correct_list(const RsDevTables *tab, const RsCorrParams *prm, uin
  *   rsk_bm     Berlekamp-Massey + Omega -> ws.lam / ws.om / ws.meta; clean
  *              codewords finished; deg != L or L > 16 -> ws.list
  *   rsk_chien  root map -> ws.roots; root count != deg finished (failure)
+ *   rsk_forney_apply  magnitudes, ok / corrected, and the corrections into the
+ *              codewords; or, as two launches (api.cpp decode_tail):
  *   rsk_forney magnitudes -> ws.roots (as correction records), ok / corrected
  *   rsk_apply  the corrections into the codewords
  * then rsk_correct_list over ws.list.  Needs RsCorrParams.vfast.
@@ -304,6 +306,11 @@ hipError_t rsk_forney(const RsDevTables *tab, const RsCorrParams *prm, const RsS
                       int num_cu, hipStream_t stream);
 hipError_t rsk_apply(const RsCorrParams *prm, const RsSplitWs *ws, uint8_t *data, size_t dstride, uint8_t *parity,
                      size_t pstride, size_t count, hipStream_t stream);
+/* rsk_forney and rsk_apply (npar = 32) or rsk_apply_nr in one kernel: the correction records stay in registers
+ * (ws.roots keeps the root lists) */
+hipError_t rsk_forney_apply(const RsDevTables *tab, const RsCorrParams *prm, const RsSplitWs *ws, uint8_t *data,
+                            size_t dstride, uint8_t *parity, size_t pstride, size_t count, uint32_t npar, uint8_t *ok,
+                            uint8_t *corrected, int num_cu, hipStream_t stream);
 
 /*
  * The same split decode for a byte-symbol code of npar < 32 roots (tab from

@@ -9,8 +9,11 @@
  *   rs_bm_k      syndromes -> Berlekamp-Massey (src/decode.c:49-96) -> Lambda,
  *                degree (:98-110), Omega (:147-158)
  *   rs_chien_k   Lambda -> root map over the 255 points (:112-145)
- *   rs_forney_k  roots, Omega, Lambda -> Forney magnitudes (:159-191), apply
- *                (:215-226)
+ *   rs_forney_apply_k  roots, Omega, Lambda -> Forney magnitudes (:159-191)
+ *                and the corrections (:215-226) in one launch; as two,
+ *                rs_forney_k and rs_apply_k<16>, with POPORON_AMD_DECODE_TAIL=split
+ *                or under POPORON_AMD_DECODE_PATH=split
+ *                (rs_apply_k<32> serves the erasure and errata paths)
  *
  * Fast path = the codewords the reference corrects without its re-syndrome
  * check being able to fail: deg(Lambda) = L <= 16 (then Lambda has deg
@@ -919,6 +922,231 @@ __global__ __launch_bounds__(AWG) void rs_apply_k(const uint8_t *__restrict__ me
 }
 
 /* ------------------------------------------------------------------------ */
+/* rs_forney_apply_k: magnitudes and corrections in one kernel               */
+/* ------------------------------------------------------------------------ */
+
+/*
+ * rs_forney_k and rs_apply_k<16> as one kernel: the 32-byte correction record
+ * stays in the lane's registers instead of going through ws->roots, and the
+ * waves of a workgroup that are in their Forney phase (LDS lookups, VALU)
+ * share the CU with those streaming rows (HBM).  One wave per 64 codewords,
+ * as both kernels.  Wire layout, whole waves: the first FA_PRE quarter
+ * blocks (16 rows, 4,080 B, 4 x 16 B per lane) are requested before the
+ * Forney arithmetic -- after the loads of Omega, Lambda and the roots, so
+ * that the arithmetic waits for those alone (loads return in order) -- and
+ * the rest once its registers are free; each quarter then goes through the
+ * wave's 4 KiB staging buffer, where lanes 16q..16q+15 XOR their magnitudes
+ * in, and back out with 16-byte stores.  Loads and stores are non-temporal
+ * as in rs_apply_k; rows that are not on the fast path go back unchanged.
+ * Other layouts and a batch's last partial wave correct byte by byte.
+ * LDS: the 64 KiB table + 16 x 4 KiB = 128 KiB, one workgroup per CU at
+ * 4 waves/SIMD (<= 128 VGPRs).
+ */
+#define FAWG 1024
+#define FAQ 255u /* 16-byte chunks per quarter block */
+#ifndef FA_PRE
+#define FA_PRE 2 /* quarter blocks requested before the Forney arithmetic */
+#endif
+
+/* The arithmetic of rs_forney_k, statement for statement, for one codeword
+ * per lane (deg roots in rl, 0 for a lane that is not on the fast path): 16
+ * positions and 16 magnitudes packed bytewise (a magnitude 0 corrects
+ * nothing); returns the number of corrections.  (rs_forney_k keeps its own
+ * copy: calling this from it costs it 2 VGPRs, and scratch for P11 = false.) */
+template <bool P11>
+__device__ __forceinline__ uint32_t forney_lane(const GfA gf, const uint32_t fcr, const uint32_t iprim,
+                                                const int32_t pad, uint32_t deg, const uint4 o4, const uint4 l4,
+                                                const uint32_t (&rl)[4], uint32_t (&posp)[4], uint32_t (&magp)[4])
+{
+    constexpr bool fcr1 = P11, iprim1 = P11;
+    constexpr int R = FORNEY_R;
+    const uint32_t mp = 255u * 128u + gf.pofs; /* alpha^(log a - log b) = expa(loga a - loga b + mp) */
+    const uint32_t ow[4] = {o4.x, o4.y, o4.z, o4.w}, lw[4] = {l4.x, l4.y, l4.z, l4.w};
+    const uint32_t dtop = deg ? (deg - 1u) & ~1u : 0u;
+    uint32_t opu[16], lod[8]; /* address-form logs: Omega_m; Lambda_(2h+1) for 2h <= dtop */
+#pragma unroll
+    for (int m = 0; m < 16; ++m)
+        opu[m] = gf.afrom((ow[m >> 2] >> (8 * (m & 3))) & 0xffu);
+#pragma unroll
+    for (int h = 0; h < 8; ++h)
+        lod[h] = (uint32_t)(2 * h) <= dtop ? gf.afrom((lw[(2 * h) >> 2] >> (8 * ((2 * h) & 3))) & 0xffu) : gf.az();
+    const uint32_t degmax = wave_max(deg);
+    uint32_t fixed = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        posp[k] = magp[k] = 0;
+#pragma unroll
+    for (int n0 = 0; n0 < 16; n0 += R) {
+        if ((uint32_t)n0 >= degmax) /* uniform */
+            continue;
+        uint32_t ir[R], si[R], s[R], num[R], den[R], nh[R], dh[R];
+#pragma unroll
+        for (int t = 0; t < R; ++t) {
+            ir[t] = root_point((rl[(n0 + t) >> 2] >> (8 * ((n0 + t) & 3))) & 0xffu);
+            si[t] = 128u * (ir[t] == 255u ? 0u : ir[t]);
+            s[t] = num[t] = den[t] = nh[t] = dh[t] = 0;
+        }
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+#pragma unroll
+            for (int t = 0; t < R; ++t) {
+                num[t] ^= gf.expa(opu[b] + s[t]);
+                nh[t] ^= gf.expa(opu[b + 8] + s[t]);
+                if ((b & 1) == 0) {
+                    den[t] ^= gf.expa(lod[b >> 1] + s[t]);
+                    dh[t] ^= gf.expa(lod[(b >> 1) + 4] + s[t]);
+                }
+                s[t] = addmod7(s[t], si[t]);
+            }
+            if (b & 1) {
+#pragma unroll
+                for (int t = 0; t < R; ++t)
+                    asm volatile("" : "+v"(num[t]), "+v"(den[t]), "+v"(nh[t]), "+v"(dh[t]));
+                __builtin_amdgcn_sched_barrier(0); /* two powers at a time: registers */
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < R; ++t) { /* s = 128 (8 i mod 255) */
+            num[t] ^= gf.expa(gf.loga(nh[t]) + s[t]);
+            den[t] ^= gf.expa(gf.loga(dh[t]) + s[t]);
+            uint32_t mag;
+            if constexpr (fcr1) {
+                /* alpha^(log num + 255 - log den) straight from the address
+                 * forms: 128 (log num - log den + 255) + pofs is inside the
+                 * exp table's two periods (den != 0 at the distinct roots of
+                 * the fast path) */
+                mag = gf.expa(gf.loga(num[t]) - gf.loga(den[t]) + mp);
+            } else {
+                const uint32_t ln2 = mod255((uint32_t)((int32_t)ir[t] * ((int32_t)fcr - 1) + (int32_t)RS_NN));
+                const uint32_t lden = gf.plog(gf.loga(den[t])); /* log 0 = 255 in the reference: no den = 0 guard */
+                mag = gf.exp(red(gf.plog(gf.loga(num[t])) + ln2 + RS_NN - lden));
+            }
+            const bool z = (uint32_t)(n0 + t) < deg && num[t] != 0u;
+            fixed += z ? 1u : 0u;
+            const uint32_t k = iprim1 ? ir[t] - 1u : (ir[t] * iprim + 254u) % 255u;
+            const uint32_t p = (uint32_t)((int32_t)k - pad);
+            posp[(n0 + t) >> 2] |= (p & 0xffu) << (8 * ((n0 + t) & 3));
+            magp[(n0 + t) >> 2] |= (z ? mag : 0u) << (8 * ((n0 + t) & 3));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return fixed;
+}
+
+template <bool P11>
+__global__ __launch_bounds__(FAWG, FAWG / 256) void rs_forney_apply_k(
+    const RsDevTables *__restrict__ T, RsCorrParams P, uint8_t *data, size_t dstride, uint8_t *parity, size_t pstride,
+    size_t count, const uint8_t *__restrict__ lam, const uint8_t *__restrict__ om, const uint8_t *__restrict__ roots,
+    const uint8_t *__restrict__ meta, uint8_t *__restrict__ ok, uint8_t *__restrict__ corrected, uint32_t wire,
+    uint32_t npar)
+{
+    __shared__ uint32_t lgf[512 * 32];
+    __shared__ uint4 stage[FAWG / 64][256];
+    fill_gfa<FAWG>(lgf, T);
+    __syncthreads();
+    const GfA gf{lds_addr(lgf) + 4u * (threadIdx.x & 31u) + 1u};
+    const uint32_t lane = threadIdx.x & 63u;
+    uint4 *st = stage[threadIdx.x >> 6];
+    /* positions past the codeword are never written (rs_apply_k) */
+    const uint32_t lim = P.size + npar;
+    const size_t nb = (count + FAWG - 1) / FAWG;
+
+    for (size_t b = blockIdx.x; b < nb; b += gridDim.x) {
+        /* last batches first: the codewords the syndrome pass read last may still sit in the MALL */
+        const size_t wbase = (nb - 1u - b) * FAWG + (threadIdx.x & ~63u);
+        const size_t cw = wbase + lane;
+        const bool valid = cw < count;
+        const uint32_t mt = valid ? meta[cw] : 0u;
+        const bool fast = (mt >> 5) == RS_ST_FAST;
+        if (__ballot(fast) == 0ull)
+            continue;
+        const uint32_t deg = fast ? (mt & 31u) : 0u;
+        uint4 o4 = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu), l4 = o4;
+        uint32_t rl[4] = {0, 0, 0, 0};
+        if (fast) {
+            o4 = reinterpret_cast<const uint4 *>(om)[cw];
+            l4 = reinterpret_cast<const uint4 *>(lam)[cw];
+            const uint4 ra = reinterpret_cast<const uint4 *>(roots)[2 * cw];
+            rl[0] = ra.x, rl[1] = ra.y, rl[2] = ra.z, rl[3] = ra.w;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const bool block = wire && wbase + 64u <= count; /* uniform */
+        lds_u32x4_t *rows = reinterpret_cast<lds_u32x4_t *>(data + wbase * 255u);
+        /* chunk lane + 64 k of a quarter; lane 63 has no fourth one and reads chunk 254 again */
+        const uint32_t c3 = min(lane + 192u, FAQ - 1u);
+        /* requested on every path (from the table image where there is no block to read), so that the
+         * count of loads in flight behind Omega, Lambda and the roots is known at compile time */
+        const lds_u32x4_t *pre = block ? rows : reinterpret_cast<const lds_u32x4_t *>(T->gfa);
+        lds_u32x4_t v[4][4];
+#pragma unroll
+        for (int q = 0; q < FA_PRE; ++q)
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k)
+                v[q][k] = __builtin_nontemporal_load(pre + FAQ * q + (k < 3 ? lane + 64u * k : c3));
+        __builtin_amdgcn_sched_barrier(0);
+        uint32_t posp[4], magp[4];
+        const uint32_t fixed = forney_lane<P11>(gf, P.fcr, P.iprim, P.pad, deg, o4, l4, rl, posp, magp);
+        if (fast) {
+            ok[cw] = 1;
+            if (corrected)
+                corrected[cw] = (uint8_t)fixed;
+        }
+        if (block) {
+#pragma unroll
+            for (int q = FA_PRE; q < 4; ++q)
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                    v[q][k] = __builtin_nontemporal_load(rows + FAQ * q + (k < 3 ? lane + 64u * k : c3));
+            uint32_t *stw = reinterpret_cast<uint32_t *>(st);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                    if (lane + 64u * k < FAQ)
+                        st[lane + 64u * k] = make_uint4(v[q][k].x, v[q][k].y, v[q][k].z, v[q][k].w);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if ((lane >> 4) == (uint32_t)q) {
+#pragma unroll
+                    for (int n = 0; n < 16; ++n) {
+                        const uint32_t mg = (magp[n >> 2] >> (8 * (n & 3))) & 0xffu;
+                        const uint32_t p = (posp[n >> 2] >> (8 * (n & 3))) & 0xffu;
+                        if (mg && p < lim) { /* p < 255: inside the lane's row of the quarter */
+                            const uint32_t a = (lane & 15u) * 255u + p;
+                            atomicXor(stw + (a >> 2), mg << (8u * (a & 3u)));
+                        }
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                    if (lane + 64u * k < FAQ) {
+                        const uint4 r = st[lane + 64u * k];
+                        __builtin_nontemporal_store(lds_u32x4_t{r.x, r.y, r.z, r.w}, rows + FAQ * q + lane + 64u * k);
+                    }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+        } else if (fast) {
+            uint8_t *cdata = data + cw * dstride, *cpar = parity + cw * pstride;
+#pragma unroll
+            for (int n = 0; n < 16; ++n) {
+                const uint32_t mg = (magp[n >> 2] >> (8 * (n & 3))) & 0xffu;
+                const uint32_t p = (posp[n >> 2] >> (8 * (n & 3))) & 0xffu;
+                if (mg && p < lim) {
+                    uint8_t *d = p < P.size ? cdata + p : cpar + (p - P.size);
+                    *d = (uint8_t)(*d ^ mg);
+                }
+            }
+        }
+    }
+}
+
+/* ------------------------------------------------------------------------ */
 /* launchers                                                                 */
 /* ------------------------------------------------------------------------ */
 
@@ -970,6 +1198,28 @@ extern "C" hipError_t rsk_forney(const RsDevTables *tab, const RsCorrParams *prm
     else
         RS_LAUNCH(rs_forney_k<false>, grid, dim3(F2WG), 0, stream, tab, *prm, data, dstride, parity, pstride, count,
                   ws->lam, ws->om, ws->roots, ws->meta, ok, corrected);
+    return hipGetLastError();
+}
+
+/* rsk_forney and rsk_apply / rsk_apply_nr (npar < 32) in one launch */
+extern "C" hipError_t rsk_forney_apply(const RsDevTables *tab, const RsCorrParams *prm, const RsSplitWs *ws,
+                                       uint8_t *data, size_t dstride, uint8_t *parity, size_t pstride, size_t count,
+                                       uint32_t npar, uint8_t *ok, uint8_t *corrected, int num_cu, hipStream_t stream)
+{
+    if (count == 0)
+        return hipSuccess;
+    const uint32_t wire = prm->size + npar == 255u && dstride == 255u && pstride == 255u &&
+                          parity == data + prm->size && (reinterpret_cast<uintptr_t>(data) & 15u) == 0u;
+    /* one workgroup per CU, each looping over its batches: 0.115 ms per 2^20 codewords against 0.117-0.118
+     * for one batch per workgroup, which fills the table four times per CU (profiles/forney_apply_variants.log) */
+    const size_t need = (count + FAWG - 1) / FAWG, cap = (size_t)(num_cu > 0 ? num_cu : 256);
+    const dim3 grid((uint32_t)(need < cap ? need : cap));
+    if (prm->fcr == 1u && prm->iprim == 1u)
+        RS_LAUNCH(rs_forney_apply_k<true>, grid, dim3(FAWG), 0, stream, tab, *prm, data, dstride, parity, pstride,
+                  count, ws->lam, ws->om, ws->roots, ws->meta, ok, corrected, wire, npar);
+    else
+        RS_LAUNCH(rs_forney_apply_k<false>, grid, dim3(FAWG), 0, stream, tab, *prm, data, dstride, parity, pstride,
+                  count, ws->lam, ws->om, ws->roots, ws->meta, ok, corrected, wire, npar);
     return hipGetLastError();
 }
 
