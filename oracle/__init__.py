@@ -277,6 +277,11 @@ class BchOracle:
         L.oracle_bch_data_bits.restype = L.oracle_bch_parity_bits.restype = C.c_uint32
         L.oracle_bch_encode.argtypes = [C.c_void_p, _u8p, C.c_size_t, _u8p]
         L.oracle_bch_decode.argtypes = [C.c_void_p, _u8p, C.c_size_t, _u8p, C.POINTER(C.c_size_t)]
+        L.oracle_bch_encode_batch.argtypes = [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.c_size_t, C.c_size_t]
+        L.oracle_bch_encode_batch.restype = C.c_size_t
+        L.oracle_bch_decode_batch.argtypes = [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                              _u8p, _u32p]
+        L.oracle_bch_decode_batch.restype = None
         self._buf = C.create_string_buffer(L.oracle_bch_sizeof())
         self.h = C.cast(self._buf, C.c_void_p)
         rc = L.oracle_bch_init(self.h, m, poly, t)
@@ -301,6 +306,53 @@ class BchOracle:
         ok = self.lib.oracle_bch_decode(self.h, _ptr(d) if d.size else _ptr(np.zeros(1, np.uint8)), d.size,
                                         _ptr(p) if p.size else _ptr(np.zeros(1, np.uint8)), C.byref(n))
         return bool(ok), int(n.value), d
+
+    # -- received words <-> the byte images of poporon_encode / poporon_decode ------
+    def word_images(self, words, junk=None):
+        """Big-endian byte images of nn-bit words (data bits above the parity bits):
+        data (count, max(1, data_bytes)), parity (count, parity_bytes).  Where junk[c] is
+        odd, the bits of the top data / parity byte that lie above k / pbits are set (the
+        codec masks them on read).  A k = 0 code has an empty data image; its one data
+        byte (poporon_decode wants size >= 1) carries the row number and is never used."""
+        w = np.asarray(words, dtype=np.uint64)
+        j = np.zeros(w.shape, np.uint64) if junk is None else (np.asarray(junk).astype(np.uint64) & np.uint64(1))
+        out = []
+        for val, bits, nb in ((w >> np.uint64(self.pbits), self.k, self.data_bytes),
+                              (w & np.uint64((1 << self.pbits) - 1), self.pbits, self.parity_bytes)):
+            val = val | j * np.uint64(((1 << (8 * nb)) - 1) ^ ((1 << bits) - 1))
+            img = np.zeros((w.size, nb), np.uint8)
+            for i in range(nb):
+                img[:, nb - 1 - i] = (val >> np.uint64(8 * i)) & np.uint64(0xFF)
+            out.append(img)
+        if self.data_bytes == 0:
+            out[0] = (np.arange(w.size) & 0xFF).astype(np.uint8)[:, None]
+        return out[0], out[1]
+
+    # -- batches (loops over the two single-codeword functions, in C) -------------
+    def encode_batch(self, data):
+        """data (count, size >= data_bytes) byte images -> parity (count, parity_bytes)."""
+        d = np.ascontiguousarray(data, dtype=np.uint8)
+        count, size = d.shape
+        par = np.zeros((count, self.parity_bytes), np.uint8)
+        src = d if d.size else np.zeros(1, np.uint8)  # k = 0: nothing is read
+        bad = self.lib.oracle_bch_encode_batch(self.h, _ptr(src), size, _ptr(par), self.parity_bytes, size, count)
+        if bad:
+            raise ValueError(f"oracle_bch_encode refused {bad} rows (size {size} < {self.data_bytes})")
+        return par
+
+    def decode_batch(self, data, parity):
+        """data (count, size), parity (count, parity_bytes).  Returns (ok u8[count],
+        corrected u32[count], data'): rows rewritten on success only, corrected 0 on failure."""
+        d = np.array(data, dtype=np.uint8, copy=True, order="C")
+        p = np.ascontiguousarray(parity, dtype=np.uint8)
+        count, size = d.shape
+        assert p.shape == (count, self.parity_bytes)
+        ok = np.zeros(count, np.uint8)
+        cor = np.zeros(count, np.uint32)
+        if count and size:
+            self.lib.oracle_bch_decode_batch(self.h, _ptr(d), size, _ptr(p), self.parity_bytes, size, count, _ptr(ok),
+                                             _ptr(cor, _u32p))
+        return ok, cor, d
 
 
 class ReferenceBch:

@@ -281,3 +281,28 @@ int oracle_bch_decode(const oracle_bch_t *b, uint8_t *data, size_t size, const u
         *corrected = ne > 0 ? (size_t)ne : 0;
     return 1;
 }
+
+/* Batch helpers (loops over the single-codeword functions) for test speed:
+ * rows data_stride / parity_stride bytes apart, each row's data image `size`
+ * bytes long.  Encode returns the number of rows oracle_bch_encode refused. */
+size_t oracle_bch_encode_batch(const oracle_bch_t *b, const uint8_t *data, size_t data_stride, uint8_t *parity,
+                               size_t parity_stride, size_t size, size_t count)
+{
+    size_t c, bad = 0;
+    for (c = 0; c < count; c++)
+        bad += !oracle_bch_encode(b, data + c * data_stride, size, parity + c * parity_stride);
+    return bad;
+}
+
+/* ok[c] = the bool of oracle_bch_decode; corrected[c] = its *corrected (0 on
+ * failure, which leaves the row as it was). */
+void oracle_bch_decode_batch(const oracle_bch_t *b, uint8_t *data, size_t data_stride, const uint8_t *parity,
+                             size_t parity_stride, size_t size, size_t count, uint8_t *ok, uint32_t *corrected)
+{
+    size_t c;
+    for (c = 0; c < count; c++) {
+        size_t n = 0;
+        ok[c] = (uint8_t)oracle_bch_decode(b, data + c * data_stride, size, parity + c * parity_stride, &n);
+        corrected[c] = ok[c] ? (uint32_t)n : 0;
+    }
+}

@@ -210,3 +210,75 @@ def test_bch_oracle_vs_reference_random():
             assert (o.encode(d)[1] == r.encode(d)[1]).all()
             a, b = o.decode(d, p, 5), r.decode(d, p, 5)
             assert a[0] == b[0] and a[1] == b[1] and (a[2] == b[2]).all()
+
+
+def _bch_single_loop(o, data, parity, size):
+    """(ok, corrected, data') of the single-codeword oracle, one call per row"""
+    ok = np.zeros(len(data), np.uint8)
+    cor = np.zeros(len(data), np.uint32)
+    out = data.copy()
+    for c in range(len(data)):
+        g, n, d = o.decode(data[c, :size], parity[c], 777)
+        assert g or n == 777  # corrected_num is left alone on failure
+        ok[c], cor[c] = g, n if g else 0
+        out[c, :size] = d
+    return ok, cor, out
+
+
+@pytest.mark.parametrize("m,poly,t,nwords", [(4, 0x13, 3, None), (3, 0x0B, 2, None), (5, 0x25, 5, 4096)])
+def test_bch_oracle_batch_equals_single(m, poly, t, nwords):
+    """oracle_bch_encode_batch / oracle_bch_decode_batch are loops over the
+    single-codeword functions: every word of the two small codes (unused high
+    bits of the top bytes set on odd rows) and 4096 random 31-bit words."""
+    from oracle import BchOracle
+    o = BchOracle(m, poly, t)
+    nn = (1 << m) - 1
+    words = (np.arange(1 << nn, dtype=np.uint64) if nwords is None
+             else np.random.default_rng(55).integers(0, 1 << nn, nwords, dtype=np.uint64))
+    data, parity = o.word_images(words, junk=np.arange(len(words)))
+    assert data.shape[1] == o.data_bytes and parity.shape[1] == o.parity_bytes
+    ok, cor, out = o.decode_batch(data, parity)
+    wok, wcor, wout = _bch_single_loop(o, data, parity, o.data_bytes)
+    assert (ok == wok).all() and (cor == wcor).all() and (out == wout).all()
+    assert 0 < ok.sum() < len(ok) or t * 2 + 1 >= nn
+    # a data image longer than data_bytes: only the first data_bytes are read or written
+    wide = np.concatenate([data, np.full((len(data), 2), 0xA5, np.uint8)], 1)
+    ok2, cor2, out2 = o.decode_batch(wide, parity)
+    assert (ok2 == ok).all() and (cor2 == cor).all() and (out2[:, :o.data_bytes] == out).all()
+    assert (out2[:, o.data_bytes:] == 0xA5).all()
+    # encode: every message (or the words' data images), batch == single
+    msgs = data if nwords is not None else o.word_images(np.arange(1 << o.k, dtype=np.uint64) << np.uint64(o.pbits),
+                                                         junk=np.arange(1 << o.k))[0]
+    par = o.encode_batch(msgs)
+    for c in range(len(msgs)):
+        g, p = o.encode(msgs[c])
+        assert g and (p == par[c]).all(), c
+    with pytest.raises(ValueError):
+        o.encode_batch(msgs[:, : o.data_bytes - 1])
+
+
+@pytest.mark.skipif(not reference_available(), reason="oracle/_ref not built here")
+def test_bch_oracle_vs_reference_exhaustive():
+    """Oracle == compiled reference on every received word of every accepted
+    m = 3 code (t = 1..16, k = 0 codes included) and of (4, 0x13) at
+    t = 1, 2, 3, 4, 7, 8, 12, 16 (k = 1 at t = 4, 7; k = 0 from t = 8): the
+    bool, corrected_num (left at its initial value on failure) and the data
+    bytes, with the unused high bits of the top bytes set on odd rows."""
+    from oracle import BchOracle, ReferenceBch
+    cases = [(3, p, t) for p in (0x0B, 0x0D) for t in range(1, 17)]
+    cases += [(4, 0x13, t) for t in (1, 2, 3, 4, 7, 8, 12, 16)]
+    for m, poly, t in cases:
+        o, r = BchOracle(m, poly, t), ReferenceBch(m, poly, t)
+        assert (o.parity_bytes, o.data_bytes) == (r.parity_bytes, r.info_bytes), (m, poly, t)
+        n = 1 << ((1 << m) - 1)
+        data, parity = o.word_images(np.arange(n, dtype=np.uint64), junk=np.arange(n))
+        ok, cor, out = o.decode_batch(data, parity)
+        for c in range(n):
+            g, gn, gd = r.decode(data[c], parity[c], 777)
+            assert g == bool(ok[c]) and gn == (cor[c] if g else 777) and (gd == out[c]).all(), (m, poly, t, c)
+        # every message (k = 0: the one empty message, behind a data byte nobody reads)
+        msgs = o.word_images(np.arange(1 << o.k, dtype=np.uint64) << np.uint64(o.pbits), junk=np.arange(1 << o.k))[0]
+        par = o.encode_batch(msgs)
+        for c in range(len(msgs)):
+            g, p = r.encode(msgs[c])
+            assert g and (p == par[c]).all(), (m, poly, t, c)
