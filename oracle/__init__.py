@@ -53,6 +53,9 @@ class Oracle:
         L.oracle_rs_encode_batch.argtypes = [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.c_size_t, C.c_size_t]
         L.oracle_rs_decode_batch.argtypes = [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.c_size_t, C.c_size_t,
                                              C.c_int, _u32p, C.c_size_t, _u32p, _u8p, _u32p]
+        L.oracle_rs_syndrome_batch.argtypes = [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                               _u16p, C.c_size_t, _u8p]
+        L.oracle_rs_syndrome_batch.restype = None
         L.oracle_rs_encode_batch_mt.argtypes = L.oracle_rs_encode_batch.argtypes + [C.c_int]
         L.oracle_rs_decode_batch_mt.argtypes = L.oracle_rs_decode_batch.argtypes + [C.c_int]
         self._buf = C.create_string_buffer(L.oracle_rs_sizeof())
@@ -121,6 +124,40 @@ class Oracle:
         else:
             self.lib.oracle_rs_encode_batch(self.h, _ptr(data), size, _ptr(par), self.nroots, size, count)
         return par
+
+    def syndrome_batch(self, data, parity):
+        """(nonzero u8[count], log-form syndromes u16[count, nroots]): oracle_rs_syndrome per row."""
+        d = np.ascontiguousarray(data, dtype=np.uint8)
+        p = np.ascontiguousarray(parity, dtype=np.uint8)
+        count, size = d.shape
+        syn = np.zeros((count, self.nroots), np.uint16)
+        flag = np.zeros(count, np.uint8)
+        self.lib.oracle_rs_syndrome_batch(self.h, _ptr(d), size, _ptr(p), p.shape[1], size, count, _ptr(syn, _u16p),
+                                          self.nroots, _ptr(flag))
+        return flag, syn
+
+    def syndrome_sweep(self, size, seed=0):
+        """One row per syndrome vector of the code: (data, parity) of 2^(m nroots) rows
+        [base | encode(base) ^ v], v running over every value of the nroots parity symbols
+        (the base-2^m digits of the row number, digit j in parity byte j).  The syndromes
+        are linear in the row and the parity symbols alone already reach every vector, so
+        each vector appears exactly once.  base: `size` raw bytes 0..255 from a seeded
+        generator (the codec masks to m bits on read); on odd rows the parity bytes also
+        carry random bits above bit m, which a correction must leave in place."""
+        m, nr, nn = self.m, self.nroots, self.nn
+        rng = np.random.default_rng([seed, m, nr, size])
+        base = rng.integers(0, 256, size, dtype=np.uint8)
+        n = 1 << (m * nr)
+        rows = np.arange(n, dtype=np.uint64)
+        parity = np.empty((n, nr), np.uint8)
+        par = self.encode(base)
+        for j in range(nr):
+            parity[:, j] = ((rows >> np.uint64(m * j)) & np.uint64(nn)).astype(np.uint8) ^ par[j]
+        if m < 8:
+            junk = rng.integers(0, 256, (n, nr), dtype=np.uint8) & np.uint8(0xFF ^ nn)
+            junk[0::2] = 0
+            parity |= junk
+        return np.tile(base, (n, 1)), parity
 
     def decode_batch(self, data, parity, erasures=None, counts=None, threads=0):
         """data (count,size), parity (count,nroots); erasures (count, >=nroots) uint32 slots + counts.

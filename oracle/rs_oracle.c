@@ -364,6 +364,16 @@ void oracle_rs_decode_batch(const oracle_rs_t *rs, uint8_t *data, size_t data_st
     }
 }
 
+void oracle_rs_syndrome_batch(const oracle_rs_t *rs, const uint8_t *data, size_t data_stride, const uint8_t *parity,
+                              size_t parity_stride, size_t size, size_t count, uint16_t *syn, size_t syn_stride,
+                              uint8_t *nonzero)
+{
+    size_t c;
+    for (c = 0; c < count; c++)
+        nonzero[c] = (uint8_t)oracle_rs_syndrome(rs, data + c * data_stride, size, parity + c * parity_stride,
+                                                 syn + c * syn_stride);
+}
+
 typedef struct {
     const oracle_rs_t *rs;
     uint8_t *data, *parity;

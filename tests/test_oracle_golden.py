@@ -282,3 +282,106 @@ def test_bch_oracle_vs_reference_exhaustive():
         for c in range(len(msgs)):
             g, p = r.encode(msgs[c])
             assert g and (p == par[c]).all(), (m, poly, t, c)
+
+
+# ---------------------------------------------------------------------------
+# every syndrome vector of the small-root codes (tests/test_gpu_rs_exhaustive.py
+# decodes the same tables on the GPU and takes the oracle's word for them)
+# ---------------------------------------------------------------------------
+def test_syndrome_sweep_reaches_every_vector():
+    """Oracle.syndrome_sweep: 2^(m nr) rows whose syndrome vectors are all different, bits
+    above the symbol set in the parity bytes of odd rows only; oracle_rs_syndrome_batch is
+    a loop over the single-codeword function."""
+    for code, size in (((3, 0xB, 1, 1, 3), 4), ((4, 0x13, 1, 2, 2), 1), ((5, 0x25, 3, 1, 2), 14),
+                       ((8, 0x11D, 1, 1, 1), 254), ((2, 7, 0, 2, 1), 2)):
+        m, nr = code[0], code[4]
+        o = Oracle(*code)
+        data, parity = o.syndrome_sweep(size)
+        n = 1 << (m * nr)
+        assert data.shape == (n, size) and parity.shape == (n, nr) and (data == data[0]).all()
+        flag, syn = o.syndrome_batch(data, parity)
+        assert len({tuple(s) for s in syn}) == n and (syn <= o.nn).all()
+        assert flag[0] == 0 and flag[1:].all()
+        high = (parity >> m).any(1)
+        assert not high[0::2].any() and (m == 8 or high[1::2].sum() > n // 4)
+        for c in range(0, n, max(1, n // 64)):
+            f, s = o.syndrome(data[c], parity[c])
+            assert f == bool(flag[c]) and (s == syn[c]).all()
+
+
+def _reference_rows(r, data, parity):
+    """poporon_decode of the compiled reference on every row, in place on copies:
+    (ok, corrected_num, data', parity')"""
+    import ctypes as C
+    fn = r.lib.poporon_decode
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
+    d, p = data.copy(), parity.copy()
+    n, size = d.shape
+    nr = p.shape[1]
+    ok, cor = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+    num = C.c_size_t(0)
+    ref, d0, p0 = C.byref(num), d.ctypes.data, p.ctypes.data
+    for c in range(n):
+        num.value = 0
+        ok[c] = fn(r.h, d0 + c * size, size, p0 + c * nr, ref)
+        cor[c] = num.value
+    return ok, cor, d, p
+
+
+def _assert_rows_equal(tag, got, want):
+    for name, g, w in zip(("ok", "corrected_num", "data", "parity"), got, want):
+        bad = (g != w) if g.ndim == 1 else (g != w).any(1)
+        assert not bad.any(), (tag, name, int(np.nonzero(bad)[0][0]), int(bad.sum()))
+
+
+def _sweep_sizes(code):
+    k = (1 << code[0]) - 1 - code[4]
+    return range(1, k + 1) if code[0] <= 3 else (1, k)
+
+
+@pytest.mark.skipif(not reference_available(), reason="oracle/_ref not built here")
+@pytest.mark.parametrize("part", ["errors", "m8", "erasures"])
+def test_restatement_vs_reference_every_syndrome(part):
+    """Oracle == compiled reference (bool, corrected_num, every byte) where the GPU tests
+    lean on the oracle alone:
+    errors    the whole sweep of six small codes (corrected_num counted on a failure,
+              more than nr / 2 corrections, roots in the padding), at every size for
+              m <= 3 and at sizes 1 and k above;
+    m8        every 16th row of the byte-symbol 2-root tables at sizes 1, k / 2 and k;
+    erasures  the sweep under every erasure list of 0 .. nr positions, repeats and all
+              orders included, with every position and stale slot below `size`: past it
+              the reference writes outside data[], and the oracle's parity addressing
+              there is this project's own definition."""
+    import itertools
+    if part == "errors":
+        for code in ((2, 7, 1, 1, 2), (3, 0xB, 1, 1, 3), (3, 0xB, 1, 1, 4), (3, 0xD, 5, 2, 6), (4, 0x13, 1, 2, 3),
+                     (4, 0x13, 1, 2, 4)):
+            o, r = Oracle(*code), Reference(*code)
+            for size in ((1,) if code[4] == 6 else _sweep_sizes(code)):
+                data, parity = o.syndrome_sweep(size)
+                _assert_rows_equal((code, size), o.decode_batch(data, parity), _reference_rows(r, data, parity))
+            r.close()
+    elif part == "m8":
+        for code in ((8, 0x11D, 0, 1, 2), (8, 0x11D, 1, 1, 2), (8, 0x187, 5, 7, 2), (8, 0x171, 1, 11, 2),
+                     (8, 0x11D, 2000, 37, 2)):
+            o, r = Oracle(*code), Reference(*code)
+            for size in (1, 253 // 2, 253):
+                data, parity = o.syndrome_sweep(size)
+                data, parity = np.ascontiguousarray(data[::16]), np.ascontiguousarray(parity[::16])
+                _assert_rows_equal((code, size), o.decode_batch(data, parity), _reference_rows(r, data, parity))
+            r.close()
+    else:
+        for code, size in (((3, 0xB, 1, 1, 3), 4), ((4, 0x13, 1, 2, 2), 13)):
+            nr = code[4]
+            o, r = Oracle(*code), Reference(*code, erasure=True)
+            data, parity = o.syndrome_sweep(size)
+            n = len(data)
+            lists = [t for e in range(nr + 1) for t in itertools.product(range(size), repeat=e)]
+            for li, lst in enumerate(lists):
+                slots = np.array([(5 * li + 3 * j + 1) % size for j in range(nr)], np.uint32)
+                slots[:len(lst)] = lst
+                r.set_erasures(slots)  # the stale slots stay in the object behind the count
+                r.set_erasures(lst)
+                want = o.decode_batch(data, parity, np.tile(slots, (n, 1)), np.full(n, len(lst), np.uint32))
+                _assert_rows_equal((code, size, lst), want, _reference_rows(r, data, parity))
+            r.close()
