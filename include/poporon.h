@@ -3,13 +3,20 @@
  *
  * Same symbols, signatures, enums and macros as the reference's
  * include/poporon.h:22-99 (libpoporon, colopl/libpoporon), so existing
- * callers recompile and relink unchanged.  The Reed-Solomon and BCH codecs
- * are served by HIP kernels; LDPC is outside this build's scope: its config
- * constructors are exported so callers still link, but return NULL.
+ * callers recompile and relink unchanged.  The Reed-Solomon, BCH and LDPC
+ * codecs are served by HIP kernels.  Only the two LDPC convenience
+ * constructors are outside this build: poporon_config_ldpc_default and
+ * poporon_config_ldpc_burst_resistant are exported so callers still link, but
+ * return NULL (a test of this repository pins that; flipping both is a
+ * two-line follow-up).  Their equivalents, from the reference's src/poporon.c:
+ *   default:         poporon_ldpc_config_create(block, rate, PPRN_LDPC_RANDOM, 3,
+ *                                               true, true, true, 0, 0, 0, NULL, 0, 0)
+ *   burst_resistant: poporon_ldpc_config_create(block, rate, PPRN_LDPC_RANDOM, 7,
+ *                                               true, true, true, 0, 0, 0, NULL, 0, 0)
  *
  *   reference symbol                     replaced by (this header)
  *   poporon_rs_config_create    poporon.h:67-69   -> same, src/api.cpp
- *   poporon_ldpc_config_create  poporon.h:71-76   -> stub, returns NULL
+ *   poporon_ldpc_config_create  poporon.h:71-76   -> same (stores its 13 arguments, borrows soft_llr)
  *   poporon_bch_config_create   poporon.h:78-79   -> same (BCH kernels, symbol_size 3..5)
  *   poporon_config_rs_default   poporon.h:81      -> same (8, 0x11D, 1, 1, 32)
  *   poporon_config_ldpc_default / _burst_resistant
@@ -17,8 +24,10 @@
  *   poporon_config_bch_default  poporon.h:84      -> same (4, 0x13, 3)
  *   poporon_config_destroy      poporon.h:85
  *   poporon_create / _destroy   poporon.h:87-88
- *   poporon_encode              poporon.h:90      -> RS / BCH encode kernel (batch of one)
- *   poporon_decode              poporon.h:91      -> RS syndrome + correction / BCH decode kernels
+ *   poporon_encode              poporon.h:90      -> RS / BCH / LDPC encode kernel (batch of one)
+ *   poporon_decode              poporon.h:91      -> RS syndrome + correction / BCH / LDPC decode kernels
+ *                                                    (LDPC: size must equal the info size; *corrected_num
+ *                                                    is the iteration count, written on success only)
  *   poporon_get_fec_type / _iterations_used / _parity_size / _info_size
  *                               poporon.h:93-96
  *   poporon_version_id / poporon_buildtime

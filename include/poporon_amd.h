@@ -23,6 +23,11 @@
  * parity rows hold the parity byte image, and there are no erasure or
  * external-syndrome variants; d_corrected[c] = 0 where d_ok[c] = 0.
  *
+ * LDPC handles (PPLN_FEC_LDPC) have batch calls of their own, poporon_ldpc_*
+ * below: their encode rewrites the data, their iteration counts do not fit a
+ * byte and their soft decode takes a third input.  The RS / BCH batch calls
+ * return false with a message on an LDPC handle.
+ *
  * Every entry point returns false and records a message (poporon_amd_last_error)
  * on invalid arguments, an unsupported configuration, or a HIP failure.  There
  * is no CPU fallback: without a usable GPU these calls fail.
@@ -66,7 +71,12 @@ bool poporon_amd_reserve(poporon_t *pprn, size_t max_count);
  * RS(255,223)-shaped parameters (symbol_size 8, num_roots 32, generator
  * without zero coefficients, (fcr+31)*prim+254 < 65536) run on the fast
  * kernels, all others on the general-parameter kernels (same results,
- * lower throughput).  False otherwise (symbol_size 1 or > 8). */
+ * lower throughput).  False otherwise (symbol_size 1 or > 8).  BCH handles:
+ * symbol_size 3..5.  LDPC handles: true unless the inner bit interleaver is
+ * not a permutation (interleave depth * width != codeword bits, e.g. block 32
+ * at rate 5/6 with the automatic depth): the reference's own decode reads
+ * uninitialised memory for such a code; the handle exists, the getters work,
+ * every codec call returns false with a message. */
 bool poporon_amd_supported(const poporon_t *pprn);
 
 /* ---- device-resident batches (asynchronous on `stream`) ------------------ */
@@ -128,6 +138,66 @@ bool poporon_decode_batch(poporon_t *pprn, uint8_t *data, size_t data_stride, ui
                           size_t size, size_t count, const uint8_t *positions, size_t positions_stride,
                           const uint8_t *counts, uint8_t *ok, uint8_t *corrected);
 
+/* ---- LDPC batches -----------------------------------------------------------
+ * Row c has info_bytes (poporon_get_info_size) of data at d_data +
+ * c*data_stride and parity_bytes (poporon_get_parity_size) of parity at
+ * d_parity + c*parity_stride; bases and strides may have any alignment, and
+ * bytes between rows are never written.  Every per-row result equals the
+ * reference's for that row, bit for bit (tests/test_gpu_ldpc.py).
+ *
+ * Encode (src/encode.c:147-197): the outer interleaver permutes the data bytes
+ * in place, parity bit i is the XOR of check row i's info bits and parity bit
+ * i-1, spare bits of the last parity byte are 0, and with the inner
+ * interleaver on the first codeword_bits bits of data and parity together are
+ * bit-interleaved: data and parity are both rewritten.
+ *
+ * Decode (src/decode.c:489-540).  d_llr == NULL: the hard path
+ * (poporon_ldpc_decode_hard): a clean row gives ok with 0 iterations, else up
+ * to max_iterations rounds of normalised min-sum from +/-30000 (a config
+ * value of 0 means 50).  d_llr given: the soft path (poporon_ldpc_decode_soft)
+ * on codeword_bits int8 values per row in channel order at d_llr +
+ * c*llr_stride; the row's data and parity bits are not read (d_parity may be
+ * NULL) and there is no iteration-0 check.
+ * d_ok[c] = result; d_iterations[c] (may be NULL) = the reference's
+ * iterations_used (max_iterations on failure); d_hard (may be NULL) gets
+ * codeword_bytes = info_bytes + parity_bytes per row, the de-interleaved hard
+ * decisions of the last iteration, for failed rows too.  d_data is rewritten
+ * (outer de-interleaved) only where d_ok[c] = 1.  Parity is never written.
+ *
+ * Check: d_dirty[c] = 1 when the de-interleaved row's syndrome is non-zero.
+ *
+ * The decoder runs one workgroup per codeword with its int16 messages in LDS
+ * when they fit the CU's 160 KiB, else in a slice of a workspace the handle
+ * owns (poporon_amd_reserve sizes it); POPORON_AMD_LDPC_PATH=lds / global in
+ * the environment at poporon_create forces either (lds on a code that does
+ * not fit fails the call).  The host forms take the same arguments without
+ * the stream and return when the results are in host memory. */
+bool poporon_ldpc_encode_batch_device(poporon_t *pprn, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                      size_t parity_stride, size_t count, void *stream);
+bool poporon_ldpc_decode_batch_device(poporon_t *pprn, uint8_t *d_data, size_t data_stride, const uint8_t *d_parity,
+                                      size_t parity_stride, const int8_t *d_llr, size_t llr_stride, size_t count,
+                                      uint8_t *d_ok, uint32_t *d_iterations, uint8_t *d_hard, size_t hard_stride,
+                                      void *stream);
+bool poporon_ldpc_check_batch_device(poporon_t *pprn, const uint8_t *d_data, size_t data_stride,
+                                     const uint8_t *d_parity, size_t parity_stride, size_t count, uint8_t *d_dirty,
+                                     void *stream);
+bool poporon_ldpc_encode_batch(poporon_t *pprn, uint8_t *data, size_t data_stride, uint8_t *parity,
+                               size_t parity_stride, size_t count);
+bool poporon_ldpc_decode_batch(poporon_t *pprn, uint8_t *data, size_t data_stride, const uint8_t *parity,
+                               size_t parity_stride, const int8_t *llr, size_t llr_stride, size_t count, uint8_t *ok,
+                               uint32_t *iterations, uint8_t *hard, size_t hard_stride);
+bool poporon_ldpc_check_batch(poporon_t *pprn, const uint8_t *data, size_t data_stride, const uint8_t *parity,
+                              size_t parity_stride, size_t count, uint8_t *dirty);
+
+/* LDPC handle's graph, owned by the handle: CSR rows of H, the inner bit
+ * interleaver's and the outer byte interleaver's forward tables
+ * (NULL when that interleaver is off).  num_edges = row_ptr[num_checks], the
+ * edges placed: the QC builder drops those whose row is >= parity_bits.
+ * Needs no GPU.  Any output pointer may be NULL. */
+bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_t *num_bits, uint32_t *num_edges,
+                            const uint32_t **row_ptr, const uint32_t **col_idx, const uint32_t **inner_forward,
+                            const uint32_t **outer_forward);
+
 /* ---- in-library kernel timing ----------------------------------------------
  * When enabled, every kernel the handle launches is bracketed by HIP events
  * recorded on the stream it runs on.  poporon_amd_timing(pprn, 1) enables and
@@ -146,6 +216,8 @@ bool poporon_decode_batch(poporon_t *pprn, uint8_t *data, size_t data_stride, ui
  * apply.  A batch of one codeword: 10 = the one-workgroup decoder
  * (rs_dec1_k), 0 = encode (rs_enc1_k).  Batches of 2..16383 codewords: 11 =
  * the one-codeword-per-wave decoder (rs_wave_k, syndromes included).
+ * LDPC handles: 12 = encode (ldpc_encode_k), 13 = decode (ldpc_decode_k),
+ * 14 = check (ldpc_check_k).
  *
  * Error- and erasure-mode batches of at least 16384 codewords take the split
  * decode; POPORON_AMD_DECODE_PATH=split / single / wave in the environment
@@ -163,6 +235,9 @@ bool poporon_decode_batch(poporon_t *pprn, uint8_t *data, size_t data_stride, ui
 #define POPORON_AMD_KERNEL_ERASURE 9
 #define POPORON_AMD_KERNEL_SINGLE 10
 #define POPORON_AMD_KERNEL_WAVE 11
+#define POPORON_AMD_KERNEL_LDPC_ENCODE 12
+#define POPORON_AMD_KERNEL_LDPC_DECODE 13
+#define POPORON_AMD_KERNEL_LDPC_CHECK 14
 bool poporon_amd_timing(poporon_t *pprn, int enable);
 bool poporon_amd_timing_read(poporon_t *pprn, int kernel, double *total_ms, uint64_t *launches);
 

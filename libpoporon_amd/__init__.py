@@ -92,6 +92,16 @@ _SIGS = {
     "poporon_amd_rng_fill_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp]),
     "poporon_syndrome_batch_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                                  _vp, C.c_size_t, _vp, _vp]),
+    "poporon_ldpc_encode_batch_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _vp]),
+    "poporon_ldpc_decode_batch_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t,
+                                                    _vp, _vp, _vp, C.c_size_t, _vp]),
+    "poporon_ldpc_check_batch_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _vp, _vp]),
+    "poporon_ldpc_encode_batch": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t]),
+    "poporon_ldpc_decode_batch": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t,
+                                             _vp, _vp, _vp, C.c_size_t]),
+    "poporon_ldpc_check_batch": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _vp]),
+    "poporon_amd_ldpc_graph": (C.c_bool, [_vp, _u32p, _u32p, _u32p, C.POINTER(_u32p), C.POINTER(_u32p),
+                                          C.POINTER(_u32p), C.POINTER(_u32p)]),
     "poporon_amd_multi_create": (_vp, [_vp, _vp, C.c_size_t]),
     "poporon_amd_multi_destroy": (None, [_vp]),
     "poporon_amd_multi_device_count": (C.c_size_t, [_vp]),
@@ -111,12 +121,18 @@ _SIGS = {
 KERNEL_ENCODE, KERNEL_REMAINDER, KERNEL_CORRECT = 0, 1, 2
 KERNEL_BM, KERNEL_CHIEN, KERNEL_FORNEY, KERNEL_LIST, KERNEL_APPLY, KERNEL_ERASURE, KERNEL_SINGLE = 4, 5, 6, 7, 8, 9, 10
 KERNEL_WAVE = 11
+KERNEL_LDPC_ENCODE, KERNEL_LDPC_DECODE, KERNEL_LDPC_CHECK = 12, 13, 14
 KERNEL_NAMES = {KERNEL_ENCODE: "rs_lfsr_k<false> (encode)", KERNEL_REMAINDER: "rs_lfsr_k<true> (remainder)",
                 KERNEL_CORRECT: "rs_correct_k (BM/Chien/Forney)", KERNEL_BM: "rs_bm_k (BM/Omega)",
                 KERNEL_CHIEN: "rs_chien_k (Chien)", KERNEL_FORNEY: "rs_forney_k (Forney)",
                 KERNEL_APPLY: "rs_apply_k (apply)", KERNEL_LIST: "rs_wave_k (list)",
                 KERNEL_ERASURE: "rs_era_bp_k (erasure)", KERNEL_SINGLE: "rs_dec1_k (one codeword)",
                 KERNEL_WAVE: "rs_wave_k (small batch)"}
+LDPC_KERNEL_NAMES = {KERNEL_LDPC_ENCODE: "ldpc_encode_k", KERNEL_LDPC_DECODE: "ldpc_decode_k",
+                     KERNEL_LDPC_CHECK: "ldpc_check_k"}
+
+LDPC_RATE_1_3, LDPC_RATE_1_2, LDPC_RATE_2_3, LDPC_RATE_3_4, LDPC_RATE_4_5, LDPC_RATE_5_6 = range(6)
+LDPC_RANDOM, LDPC_QC_RANDOM = 1, 2
 
 _lib = None
 
@@ -401,6 +417,140 @@ class Bch(Poporon):
         ok = self.lib.poporon_decode(self.h, _buf(d) if d.size else _buf(np.zeros(1, np.uint8)), d.size,
                                      _buf(p) if p.size else _buf(np.zeros(1, np.uint8)), C.byref(n))
         return bool(ok), int(n.value), d
+
+
+class Ldpc(Poporon):
+    """A PPLN_FEC_LDPC handle (poporon_ldpc_config_create + poporon_create), the
+    reference's src/ldpc.c behind ldpc_encode / ldpc_decode (src/encode.c:147-197,
+    src/decode.c:489-540).  The constructor takes poporon_ldpc_config_create's 13
+    parameters; ``soft_llr`` (codeword_bits int8) is copied once and borrowed by
+    the handle: :meth:`set_llr` rewrites it in place before a soft ``decode``.
+
+    The two convenience constructors of the C API stay stubs; their argument
+    lists are ``Ldpc(block, rate, LDPC_RANDOM, 3, True, True, True)`` (default)
+    and ``Ldpc(block, rate, LDPC_RANDOM, 7, True, True, True)`` (burst resistant).
+    """
+
+    def __init__(self, block_size, rate, matrix_type=LDPC_RANDOM, column_weight=3, use_soft_decode=False,
+                 use_outer_interleave=False, use_inner_interleave=False, interleave_depth=0, lifting_factor=0,
+                 max_iterations=0, soft_llr=None, soft_llr_size=0, seed=0, device=None):
+        self.lib = load_library()
+        self.erasure = None
+        self._syn = None
+        self._llr = None if soft_llr is None else np.array(soft_llr, dtype=np.int8, copy=True, order="C")
+        cfg = self.lib.poporon_ldpc_config_create(block_size, rate, matrix_type, column_weight, use_soft_decode,
+                                                  use_outer_interleave, use_inner_interleave, interleave_depth,
+                                                  lifting_factor, max_iterations,
+                                                  _buf(self._llr) if self._llr is not None else None,
+                                                  soft_llr_size or (self._llr.size if self._llr is not None else 0),
+                                                  seed)
+        if not cfg:
+            raise PoporonError(f"poporon_ldpc_config_create returned NULL {last_error()}")
+        self.h = self.lib.poporon_create(cfg)
+        self.lib.poporon_config_destroy(cfg)
+        if not self.h:
+            raise PoporonError(f"poporon_create returned NULL {last_error()}")
+        self.info_bytes = int(self.lib.poporon_get_info_size(self.h))
+        self.parity_bytes = int(self.lib.poporon_get_parity_size(self.h))
+        self.num_roots = self.parity_bytes  # parity bytes (array shapes of the base class)
+        self.codeword_bytes = self.info_bytes + self.parity_bytes
+        nb = C.c_uint32(0)
+        self._check(self.lib.poporon_amd_ldpc_graph(self.h, None, C.byref(nb), None, None, None, None, None),
+                    "poporon_amd_ldpc_graph")
+        self.codeword_bits = int(nb.value)
+        if device is not None:
+            self._check(self.lib.poporon_amd_set_device(self.h, device), "poporon_amd_set_device")
+
+    @property
+    def iterations_used(self):
+        return int(self.lib.poporon_get_iterations_used(self.h))
+
+    def graph(self):
+        """poporon_amd_ldpc_graph: dict of num_checks, num_bits, num_edges, row_ptr, col_idx,
+        inner_forward, outer_forward (copies; the last two None when that interleaver is off)."""
+        nc, nb, ne = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        rp, ci, inf, outf = _u32p(), _u32p(), _u32p(), _u32p()
+        self._check(self.lib.poporon_amd_ldpc_graph(self.h, C.byref(nc), C.byref(nb), C.byref(ne), C.byref(rp),
+                                                    C.byref(ci), C.byref(inf), C.byref(outf)),
+                    "poporon_amd_ldpc_graph")
+        arr = lambda p, n: np.ctypeslib.as_array(p, shape=(n,)).copy() if p else None  # noqa: E731
+        return dict(num_checks=nc.value, num_bits=nb.value, num_edges=ne.value, row_ptr=arr(rp, nc.value + 1),
+                    col_idx=arr(ci, ne.value), inner_forward=arr(inf, nb.value),
+                    outer_forward=arr(outf, self.info_bytes))
+
+    def set_llr(self, llr):
+        """Rewrite the borrowed soft_llr buffer (same size) for the next soft ``decode``."""
+        self._llr[...] = np.asarray(llr, dtype=np.int8).reshape(self._llr.shape)
+
+    # ---- single codeword ----------------------------------------------------------
+    def encode(self, data):
+        """poporon_encode: (data', parity); data' differs from data when an interleaver is on."""
+        d = _u8(data, copy=True)
+        par = np.zeros(max(self.parity_bytes, 1), np.uint8)
+        self._check(self.lib.poporon_encode(self.h, _buf(d), d.size, _buf(par)), "poporon_encode")
+        return d, par[:self.parity_bytes]
+
+    def decode(self, data, parity, corrected_init=0):
+        """poporon_decode on copies: (ok, corrected_num, data').  corrected_num is the
+        iteration count on success and stays at corrected_init on failure."""
+        d = _u8(data, copy=True)
+        p = _u8(parity, copy=True)
+        n = C.c_size_t(corrected_init)
+        ok = self.lib.poporon_decode(self.h, _buf(d), d.size, _buf(p), C.byref(n))
+        return bool(ok), int(n.value), d
+
+    # ---- host batches ---------------------------------------------------------------
+    def encode_batch(self, data):
+        """(data', parity) of every row."""
+        d = np.array(data, dtype=np.uint8, copy=True, order="C")
+        count = d.shape[0]
+        par = np.zeros((count, self.parity_bytes), np.uint8)
+        self._check(self.lib.poporon_ldpc_encode_batch(self.h, _buf(d), d.shape[1], _buf(par), self.parity_bytes,
+                                                       count), "poporon_ldpc_encode_batch")
+        return d, par
+
+    def decode_batch(self, data, parity, llr=None, want_hard=True):
+        """(ok u8[count], iterations u32[count], data', hard u8[count, codeword_bytes] or None);
+        ``llr`` (int8[count, codeword_bits]) selects the soft path."""
+        d = np.array(data, dtype=np.uint8, copy=True, order="C")
+        p = np.ascontiguousarray(parity, dtype=np.uint8)
+        count = d.shape[0]
+        ok = np.zeros(count, np.uint8)
+        it = np.zeros(count, np.uint32)
+        hard = np.zeros((count, self.codeword_bytes), np.uint8) if want_hard else None
+        l = None if llr is None else np.ascontiguousarray(llr, dtype=np.int8)
+        self._check(self.lib.poporon_ldpc_decode_batch(self.h, _buf(d), d.shape[1], _buf(p), p.shape[1],
+                                                       _buf(l) if l is not None else None,
+                                                       l.shape[1] if l is not None else 0, count, _buf(ok), _buf(it),
+                                                       _buf(hard) if want_hard else None, self.codeword_bytes),
+                    "poporon_ldpc_decode_batch")
+        return ok, it, d, hard
+
+    def check_batch(self, data, parity):
+        d = np.ascontiguousarray(data, dtype=np.uint8)
+        p = np.ascontiguousarray(parity, dtype=np.uint8)
+        dirty = np.zeros(d.shape[0], np.uint8)
+        self._check(self.lib.poporon_ldpc_check_batch(self.h, _buf(d), d.shape[1], _buf(p), p.shape[1], d.shape[0],
+                                                      _buf(dirty)), "poporon_ldpc_check_batch")
+        return dirty
+
+    # ---- device batches (pointers + hipStream_t) ---------------------------------------
+    def encode_batch_device(self, d_data, data_stride, d_parity, parity_stride, count, stream=0):
+        self._check(self.lib.poporon_ldpc_encode_batch_device(self.h, d_data, data_stride, d_parity, parity_stride,
+                                                              count, stream or None),
+                    "poporon_ldpc_encode_batch_device")
+
+    def decode_batch_device(self, d_data, data_stride, d_parity, parity_stride, count, d_ok, d_iterations=None,
+                            d_hard=None, hard_stride=0, d_llr=None, llr_stride=0, stream=0):
+        self._check(self.lib.poporon_ldpc_decode_batch_device(self.h, d_data, data_stride, d_parity, parity_stride,
+                                                              d_llr, llr_stride, count, d_ok, d_iterations, d_hard,
+                                                              hard_stride, stream or None),
+                    "poporon_ldpc_decode_batch_device")
+
+    def check_batch_device(self, d_data, data_stride, d_parity, parity_stride, count, d_dirty, stream=0):
+        self._check(self.lib.poporon_ldpc_check_batch_device(self.h, d_data, data_stride, d_parity, parity_stride,
+                                                             count, d_dirty, stream or None),
+                    "poporon_ldpc_check_batch_device")
 
 
 class Rng:

@@ -34,6 +34,8 @@
 #include "rs_device.h"
 #include "rs_generic.h"
 #include "bch_device.h"
+#include "ldpc_device.h"
+#include "ldpc_graph.h"
 
 #ifndef POPORON_BUILDTIME
 #define POPORON_BUILDTIME 1
@@ -106,9 +108,17 @@ struct _poporon_config_t {
     poporon_erasure_t *erasure;
     uint16_t *syndrome;
     uint8_t correction_capability; /* BCH */
+    /* LDPC (src/internal/config.h; soft_llr is borrowed) */
+    size_t block_size;
+    uint32_t rate, matrix_type, column_weight;
+    bool use_soft_decode, use_outer_interleave, use_inner_interleave;
+    uint32_t interleave_depth, lifting_factor, max_iterations;
+    const int8_t *soft_llr;
+    size_t soft_llr_size;
+    uint64_t seed;
 };
 
-#define NKERN 12
+#define NKERN 15
 struct TimedLaunch {
     int kernel;
     hipEvent_t a, b;
@@ -127,6 +137,9 @@ struct GpuCtx {
     RsDevTables *tab = nullptr; /* device (fast kernels) */
     RsGenTables *gtab = nullptr; /* device (general-parameter kernels) */
     uint8_t *rem = nullptr;     /* device workspace: rs_ws_bytes(rem_cap) (rs_device.h) */
+    uint32_t *ltab = nullptr;   /* device (LDPC): the graph's tables, one allocation */
+    uint8_t *lws = nullptr;     /* device (LDPC): messages of the decode kernel's workgroups, lws_bytes */
+    size_t lws_bytes = 0;
     size_t rem_cap = 0;
     /* Ordering of the workspace across streams: rem_done is recorded on the
      * stream of the last launch that read rem (rem_stream); a call on another
@@ -198,6 +211,14 @@ struct _poporon_t {
     poporon_gf_t *bgf;
     BchParams bch;
     bool bch_ok; /* codewords fit 31 bits: served by bch.hip */
+    /* PPLN_FEC_LDPC handles (rs == nullptr): the graph (owned), its device view, the decode settings */
+    LdpcGraph *ldpc;
+    LdpcDev ldev;
+    int ldpc_path; /* 0: messages in LDS when they fit, 1: LDS, 2: global workspace (POPORON_AMD_LDPC_PATH) */
+    uint32_t ldpc_max_iterations;
+    bool ldpc_soft;
+    const int8_t *ldpc_llr; /* borrowed, read at every poporon_decode */
+    uint32_t ldpc_last_iterations;
     GpuCtx gpu;
 };
 
@@ -406,14 +427,32 @@ EXPORT poporon_config_t *poporon_config_rs_default(void)
     return poporon_rs_config_create(8, 0x11D, 1, 1, 32, nullptr, nullptr);
 }
 
-/* LDPC is outside this build's scope: exported
- * so that callers link, but it constructs nothing. */
-EXPORT poporon_config_t *poporon_ldpc_config_create(size_t, poporon_ldpc_rate_t, poporon_ldpc_matrix_type_t, uint32_t,
-                                                    bool, bool, bool, uint32_t, uint32_t, uint32_t, const int8_t *,
-                                                    size_t, uint64_t)
+/* src/poporon.c:235-263: the 13 arguments are stored, soft_llr is borrowed */
+EXPORT poporon_config_t *poporon_ldpc_config_create(size_t block_size, poporon_ldpc_rate_t rate,
+                                                    poporon_ldpc_matrix_type_t matrix_type, uint32_t column_weight,
+                                                    bool use_soft_decode, bool use_outer_interleave,
+                                                    bool use_inner_interleave, uint32_t interleave_depth,
+                                                    uint32_t lifting_factor, uint32_t max_iterations,
+                                                    const int8_t *soft_llr, size_t soft_llr_size, uint64_t seed)
 {
-    fail("LDPC is not provided by libpoporon_amd");
-    return nullptr;
+    poporon_config_t *c = (poporon_config_t *)calloc(1, sizeof(poporon_config_t));
+    if (!c)
+        return nullptr;
+    c->fec_type = PPLN_FEC_LDPC;
+    c->block_size = block_size;
+    c->rate = (uint32_t)rate;
+    c->matrix_type = (uint32_t)matrix_type;
+    c->column_weight = column_weight;
+    c->use_soft_decode = use_soft_decode;
+    c->use_outer_interleave = use_outer_interleave;
+    c->use_inner_interleave = use_inner_interleave;
+    c->interleave_depth = interleave_depth;
+    c->lifting_factor = lifting_factor;
+    c->max_iterations = max_iterations;
+    c->soft_llr = soft_llr;
+    c->soft_llr_size = soft_llr_size;
+    c->seed = seed;
+    return c;
 }
 EXPORT poporon_config_t *poporon_bch_config_create(uint8_t symbol_size, uint16_t generator_polynomial,
                                                    uint8_t correction_capability)
@@ -427,14 +466,18 @@ EXPORT poporon_config_t *poporon_bch_config_create(uint8_t symbol_size, uint16_t
     c->correction_capability = correction_capability;
     return c;
 }
+/* The two LDPC convenience constructors stay stubs (tests/test_library_cpu.py
+ * pins their NULL): poporon_ldpc_config_create(block, rate, PPRN_LDPC_RANDOM,
+ * 3 (default) or 7 (burst resistant), true, true, true, 0, 0, 0, NULL, 0, 0)
+ * is what the reference's build (src/poporon.c:286-294). */
 EXPORT poporon_config_t *poporon_config_ldpc_default(size_t, poporon_ldpc_rate_t)
 {
-    fail("LDPC is not provided by libpoporon_amd");
+    fail("poporon_config_ldpc_default is a stub: use poporon_ldpc_config_create (include/poporon.h)");
     return nullptr;
 }
 EXPORT poporon_config_t *poporon_config_ldpc_burst_resistant(size_t, poporon_ldpc_rate_t)
 {
-    fail("LDPC is not provided by libpoporon_amd");
+    fail("poporon_config_ldpc_burst_resistant is a stub: use poporon_ldpc_config_create (include/poporon.h)");
     return nullptr;
 }
 EXPORT poporon_config_t *poporon_config_bch_default(void) { return poporon_bch_config_create(4, 0x13, 3); }
@@ -799,16 +842,60 @@ static poporon_t *create_bch(const poporon_config_t *config)
     return h;
 }
 
+/* src/poporon.c:112-146 over poporon_ldpc_create (src/ldpc.c:814-872): the
+ * graph is built on the host (ldpc_graph.cpp), no GPU needed.  A code whose
+ * inner interleaver is no permutation exists, answers the getters and fails
+ * every codec call (the reference decodes it through uninitialised memory). */
+static poporon_t *create_ldpc(const poporon_config_t *config)
+{
+    LdpcGraph *lg = new (std::nothrow) LdpcGraph();
+    if (!lg)
+        return nullptr;
+    if (!ldpc_graph_build(*lg, config->block_size, config->rate, config->matrix_type, config->column_weight,
+                          config->use_outer_interleave, config->use_inner_interleave, config->interleave_depth,
+                          config->lifting_factor, config->seed)) {
+        delete lg;
+        return nullptr;
+    }
+    poporon_t *h = new (std::nothrow) _poporon_t();
+    if (!h) {
+        delete lg;
+        return nullptr;
+    }
+    h->fec_type = PPLN_FEC_LDPC;
+    h->rs = nullptr;
+    h->ldpc = lg;
+    h->ldpc_max_iterations = config->max_iterations;
+    h->ldpc_soft = config->use_soft_decode;
+    h->ldpc_llr = config->soft_llr;
+    h->ldpc_last_iterations = 0;
+    h->supported = !lg->inner || lg->inner_bijective;
+    const char *lp = getenv("POPORON_AMD_LDPC_PATH");
+    h->ldpc_path = !lp ? 0 : !strcmp(lp, "lds") ? 1 : !strcmp(lp, "global") ? 2 : 0;
+    LdpcDev &v = h->ldev;
+    memset(&v, 0, sizeof(v));
+    v.info_bits = lg->info_bits;
+    v.parity_bits = lg->parity_bits;
+    v.codeword_bits = lg->codeword_bits;
+    v.info_bytes = lg->info_bytes;
+    v.parity_bytes = lg->parity_bytes;
+    v.codeword_bytes = lg->codeword_bytes;
+    v.num_checks = lg->num_checks;
+    v.num_bits = lg->num_bits;
+    v.num_edges = lg->num_edges;
+    return h;
+}
+
 EXPORT poporon_t *poporon_create(const poporon_config_t *config)
 {
     if (!config)
         return nullptr;
     if (config->fec_type == PPLN_FEC_BCH)
         return create_bch(config);
-    if (config->fec_type != PPLN_FEC_RS) {
-        fail("LDPC is not provided by libpoporon_amd");
+    if (config->fec_type == PPLN_FEC_LDPC)
+        return create_ldpc(config);
+    if (config->fec_type != PPLN_FEC_RS)
         return nullptr;
-    }
     poporon_rs_t *rs = poporon_rs_create(config->symbol_size, config->generator_polynomial,
                                          config->first_consecutive_root, config->primitive_element, config->num_roots);
     if (!rs)
@@ -977,7 +1064,8 @@ struct BatchScope {
 static void gpu_release(GpuCtx &g)
 {
     const int dev = g.device;
-    const bool any = g.ready || g.stream || g.sstream || g.tab || g.gtab || g.rem || g.stage || g.hstage || g.zc ||
+    const bool any = g.ready || g.stream || g.sstream || g.tab || g.gtab || g.rem || g.ltab || g.lws || g.stage ||
+                     g.hstage || g.zc ||
                      g.rem_done || g.registered || g.batch_ev ||
                      g.pipe[0].stream || g.pipe[1].stream || g.pipe[2].stream;
     if (!any || dev < 0) {
@@ -1006,6 +1094,8 @@ static void gpu_release(GpuCtx &g)
     (void)hipFree(g.tab);
     (void)hipFree(g.gtab);
     (void)hipFree(g.rem);
+    (void)hipFree(g.ltab);
+    (void)hipFree(g.lws);
     (void)hipFree(g.stage);
     if (g.hstage)
         (void)hipHostFree(g.hstage);
@@ -1044,11 +1134,15 @@ EXPORT void poporon_destroy(poporon_t *h)
     gpu_release(h->gpu);
     poporon_rs_destroy(h->rs);
     poporon_gf_destroy(h->bgf);
+    delete h->ldpc;
     delete h;
 }
 
 EXPORT poporon_fec_type_t poporon_get_fec_type(const poporon_t *h) { return h ? h->fec_type : PPLN_FEC_UNKNOWN; }
-EXPORT uint32_t poporon_get_iterations_used(const poporon_t *) { return 0; }
+EXPORT uint32_t poporon_get_iterations_used(const poporon_t *h)
+{
+    return h && h->fec_type == PPLN_FEC_LDPC ? h->ldpc_last_iterations : 0;
+}
 /* src/poporon.c:322-362: BCH sizes are the byte images of the parity / data bits */
 EXPORT size_t poporon_get_parity_size(const poporon_t *h)
 {
@@ -1056,6 +1150,8 @@ EXPORT size_t poporon_get_parity_size(const poporon_t *h)
         return 0;
     if (h->fec_type == PPLN_FEC_BCH)
         return h->bch_ok ? h->bch.pbytes : 0;
+    if (h->fec_type == PPLN_FEC_LDPC)
+        return h->ldpc->parity_bytes;
     return h->rs->num_roots;
 }
 EXPORT size_t poporon_get_info_size(const poporon_t *h)
@@ -1064,6 +1160,8 @@ EXPORT size_t poporon_get_info_size(const poporon_t *h)
         return 0;
     if (h->fec_type == PPLN_FEC_BCH)
         return h->bch_ok ? h->bch.dbytes : 0;
+    if (h->fec_type == PPLN_FEC_LDPC)
+        return h->ldpc->info_bytes;
     return (size_t)(h->rs->gf->field_size - h->rs->num_roots);
 }
 EXPORT uint32_t poporon_version_id(void) { return (uint32_t)POPORON_VERSION_ID; }
@@ -1128,11 +1226,46 @@ static bool batch_enter(poporon_t *h)
     return true;
 }
 
+/* the graph's tables in one device allocation; the launch parameters point into it */
+static bool ldpc_upload(poporon_t *h)
+{
+    GpuCtx &g = h->gpu;
+    const LdpcGraph &lg = *h->ldpc;
+    const std::vector<uint32_t> *src[8] = {&lg.row_ptr,       &lg.col_idx,       &lg.col_ptr,       &lg.edge_idx,
+                                           &lg.inner_forward, &lg.inner_inverse, &lg.outer_forward, &lg.outer_inverse};
+    size_t off[8], total = 0;
+    for (int i = 0; i < 8; i++) {
+        off[i] = total;
+        total += (src[i]->size() + 3) & ~(size_t)3;
+    }
+    HIP_OK(hipMalloc((void **)&g.ltab, total * sizeof(uint32_t)));
+    const uint32_t *dev[8];
+    for (int i = 0; i < 8; i++) {
+        dev[i] = src[i]->empty() ? nullptr : g.ltab + off[i];
+        if (!src[i]->empty())
+            HIP_OK(hipMemcpy(g.ltab + off[i], src[i]->data(), src[i]->size() * sizeof(uint32_t),
+                             hipMemcpyHostToDevice));
+    }
+    LdpcDev &v = h->ldev;
+    v.row_ptr = dev[0];
+    v.col_idx = dev[1];
+    v.col_ptr = dev[2];
+    v.edge_idx = dev[3];
+    v.inner_forward = dev[4];
+    v.inner_inverse = dev[5];
+    v.outer_forward = dev[6];
+    v.outer_inverse = dev[7];
+    return true;
+}
+
 static bool gpu_init_steps(poporon_t *h)
 {
     GpuCtx &g = h->gpu;
     if (h->fec_type == PPLN_FEC_BCH && !h->bch_ok)
         return fail("BCH codewords longer than 31 bits (symbol_size > 5) are not served");
+    if (h->fec_type == PPLN_FEC_LDPC && !h->supported)
+        return fail("LDPC inner interleaver is not a permutation (depth * width != codeword_bits): the reference "
+                    "decodes such a code through uninitialised memory; not served");
     if (h->fec_type == PPLN_FEC_RS && !h->supported)
         return fail("RS parameters not served by the GPU kernels (need 2 <= symbol_size <= 8 and "
                     "1 <= num_roots < 2^symbol_size - 1)");
@@ -1156,6 +1289,9 @@ static bool gpu_init_steps(poporon_t *h)
     HIP_OK(hipEventCreateWithFlags(&g.rem_done, hipEventDisableTiming));
     if (h->fec_type == PPLN_FEC_BCH) {
         /* parameters and tables go by value with every launch */
+    } else if (h->fec_type == PPLN_FEC_LDPC) {
+        if (!ldpc_upload(h))
+            return false;
     } else if (h->fast) {
         HIP_OK(hipMalloc((void **)&g.tab, sizeof(RsDevTables)));
         HIP_OK(hipMemcpy(g.tab, &h->host_tab, sizeof(RsDevTables), hipMemcpyHostToDevice));
@@ -1214,6 +1350,34 @@ static bool ensure_stage(poporon_t *h, size_t bytes)
     return true;
 }
 
+/* LDPC decode: messages in LDS (the forced or automatic choice), else in the workspace */
+static bool ldpc_use_lds(const poporon_t *h)
+{
+    return h->ldpc_path == 1 || (h->ldpc_path == 0 && ldpck_decode_lds_bytes(&h->ldev) <= LDPC_LDS_MAX);
+}
+
+/* the workspace of a decode of `count` rows: one slice per workgroup of its launch */
+static bool ldpc_reserve(poporon_t *h, size_t count)
+{
+    GpuCtx &g = h->gpu;
+    if (ldpc_use_lds(h) || count == 0)
+        return true;
+    const size_t need = (size_t)ldpck_decode_grid(&h->ldev, count, g.num_cu, false) * ldpck_slice_bytes(&h->ldev);
+    if (g.lws_bytes >= need)
+        return true;
+    if (g.lws) {
+        if (g.rem_pending)
+            HIP_OK(hipEventSynchronize(g.rem_done));
+        g.rem_pending = false;
+        HIP_OK(hipFree(g.lws));
+        g.lws = nullptr;
+        g.lws_bytes = 0;
+    }
+    HIP_OK(hipMalloc((void **)&g.lws, need));
+    g.lws_bytes = need;
+    return true;
+}
+
 EXPORT bool poporon_amd_reserve(poporon_t *h, size_t max_count)
 {
     if (!h)
@@ -1221,7 +1385,18 @@ EXPORT bool poporon_amd_reserve(poporon_t *h, size_t max_count)
     if (!gpu_init(h))
         return false;
     DeviceGuard dg(h->gpu.device);
+    if (h->fec_type == PPLN_FEC_LDPC)
+        return ldpc_reserve(h, max_count);
     return ensure_rem(h, max_count);
+}
+
+/* the RS / BCH batch calls do not serve LDPC handles: those have entry points of their own */
+static bool is_ldpc(const poporon_t *h, const char *what)
+{
+    if (h->fec_type != PPLN_FEC_LDPC)
+        return false;
+    fail("%s does not serve LDPC handles: use the poporon_ldpc_*_batch calls", what);
+    return true;
 }
 
 /* parity bytes per codeword: num_roots (RS) or the BCH parity byte image */
@@ -1900,6 +2075,8 @@ EXPORT bool poporon_encode_batch_device(poporon_t *h, const uint8_t *d_data, siz
 {
     if (!h || (count && (!d_data || !d_parity)))
         return fail("NULL argument");
+    if (is_ldpc(h, "poporon_encode_batch_device"))
+        return false;
     if (!check_encode_size(h, size))
         return false;
     if (!batch_enter(h))
@@ -1916,6 +2093,8 @@ EXPORT bool poporon_decode_batch_device(poporon_t *h, uint8_t *d_data, size_t da
 {
     if (!h || (count && (!d_data || !d_parity || !d_ok)))
         return fail("NULL argument");
+    if (is_ldpc(h, "poporon_decode_batch_device"))
+        return false;
     if (d_positions && (h->fec_type != PPLN_FEC_RS || !d_counts || positions_stride < h->rs->num_roots))
         return fail("erasure batch needs an RS handle, counts and positions_stride >= num_roots");
     if (!check_decode_size(h, size))
@@ -2030,6 +2209,8 @@ EXPORT bool poporon_encode_batch(poporon_t *h, const uint8_t *data, size_t data_
 {
     if (!h || (count && (!data || !parity)))
         return fail("NULL argument");
+    if (is_ldpc(h, "poporon_encode_batch"))
+        return false;
     if (!check_encode_size(h, size))
         return false;
     if (!batch_enter(h))
@@ -2084,6 +2265,8 @@ EXPORT bool poporon_decode_batch(poporon_t *h, uint8_t *data, size_t data_stride
 {
     if (!h || (count && (!data || !parity || !ok)))
         return fail("NULL argument");
+    if (is_ldpc(h, "poporon_decode_batch"))
+        return false;
     if (positions && (h->fec_type != PPLN_FEC_RS || !counts || positions_stride < h->rs->num_roots))
         return fail("erasure batch needs an RS handle, counts and positions_stride >= num_roots");
     if (!check_decode_size(h, size))
@@ -2167,6 +2350,255 @@ EXPORT bool poporon_decode_batch(poporon_t *h, uint8_t *data, size_t data_stride
 }
 
 /* ------------------------------------------------------------------------ */
+/* LDPC batches (ldpc.hip)                                                  */
+/* ------------------------------------------------------------------------ */
+
+EXPORT bool poporon_amd_ldpc_graph(const poporon_t *h, uint32_t *num_checks, uint32_t *num_bits, uint32_t *num_edges,
+                                   const uint32_t **row_ptr, const uint32_t **col_idx,
+                                   const uint32_t **inner_forward, const uint32_t **outer_forward)
+{
+    if (!h || h->fec_type != PPLN_FEC_LDPC)
+        return fail("poporon_amd_ldpc_graph needs an LDPC handle");
+    const LdpcGraph &lg = *h->ldpc;
+    if (num_checks)
+        *num_checks = lg.num_checks;
+    if (num_bits)
+        *num_bits = lg.num_bits;
+    if (num_edges)
+        *num_edges = lg.num_edges;
+    if (row_ptr)
+        *row_ptr = lg.row_ptr.data();
+    if (col_idx)
+        *col_idx = lg.col_idx.data();
+    if (inner_forward)
+        *inner_forward = lg.inner ? lg.inner_forward.data() : nullptr;
+    if (outer_forward)
+        *outer_forward = lg.outer ? lg.outer_forward.data() : nullptr;
+    return true;
+}
+
+/* every LDPC batch entry point: an LDPC handle whose code is served, rows
+ * that do not overlap, the device context */
+static bool ldpc_enter(poporon_t *h, const char *what, size_t data_stride, size_t parity_stride, size_t count,
+                       bool reads_parity = true)
+{
+    if (!h)
+        return fail("NULL handle");
+    if (h->fec_type != PPLN_FEC_LDPC)
+        return fail("%s serves LDPC handles", what);
+    if (count > 1 && (data_stride < h->ldpc->info_bytes || (reads_parity && parity_stride < h->ldpc->parity_bytes)))
+        return fail("%s: data_stride / parity_stride below the row sizes (%u / %u bytes)", what,
+                    (unsigned)h->ldpc->info_bytes, (unsigned)h->ldpc->parity_bytes);
+    return batch_enter(h);
+}
+
+static bool ldpc_launch_decode(poporon_t *h, uint8_t *d_data, size_t ds, const uint8_t *d_par, size_t ps,
+                               const int8_t *d_llr, size_t ls, size_t count, uint8_t *d_ok, uint32_t *d_it,
+                               uint8_t *d_hard, size_t hs, hipStream_t s)
+{
+    GpuCtx &g = h->gpu;
+    if (count == 0)
+        return true;
+    const bool lds = ldpc_use_lds(h);
+    if (lds && ldpck_decode_lds_bytes(&h->ldev) > LDPC_LDS_MAX)
+        return fail("POPORON_AMD_LDPC_PATH=lds: the code's messages (%zu bytes) do not fit the CU's %u bytes of LDS",
+                    ldpck_decode_lds_bytes(&h->ldev), (unsigned)LDPC_LDS_MAX);
+    const uint32_t grid = ldpck_decode_grid(&h->ldev, count, g.num_cu, lds);
+    if (!lds && (!ldpc_reserve(h, count) || !rem_acquire(g, s)))
+        return false;
+    KernelTimer t(g, POPORON_AMD_KERNEL_LDPC_DECODE, s);
+    HIP_OK(ldpck_decode(&h->ldev, d_data, ds, d_par, ps, d_llr, ls, count, d_ok, d_it, d_hard, hs,
+                        h->ldpc_max_iterations, lds, g.lws, grid, s));
+    t.done();
+    return lds || rem_release(g, s);
+}
+
+EXPORT bool poporon_ldpc_encode_batch_device(poporon_t *h, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                             size_t parity_stride, size_t count, void *stream)
+{
+    if (!ldpc_enter(h, "poporon_ldpc_encode_batch_device", data_stride, parity_stride, count))
+        return false;
+    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
+    if (count && (!d_data || !d_parity))
+        return fail("NULL argument");
+    DeviceGuard dg(h->gpu.device);
+    KernelTimer t(h->gpu, POPORON_AMD_KERNEL_LDPC_ENCODE, (hipStream_t)stream);
+    HIP_OK(ldpck_encode(&h->ldev, d_data, data_stride, d_parity, parity_stride, count, h->gpu.num_cu,
+                        (hipStream_t)stream));
+    t.done();
+    return true;
+}
+
+EXPORT bool poporon_ldpc_check_batch_device(poporon_t *h, const uint8_t *d_data, size_t data_stride,
+                                            const uint8_t *d_parity, size_t parity_stride, size_t count,
+                                            uint8_t *d_dirty, void *stream)
+{
+    if (!ldpc_enter(h, "poporon_ldpc_check_batch_device", data_stride, parity_stride, count))
+        return false;
+    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
+    if (count && (!d_data || !d_parity || !d_dirty))
+        return fail("NULL argument");
+    DeviceGuard dg(h->gpu.device);
+    KernelTimer t(h->gpu, POPORON_AMD_KERNEL_LDPC_CHECK, (hipStream_t)stream);
+    HIP_OK(ldpck_check(&h->ldev, d_data, data_stride, d_parity, parity_stride, count, d_dirty, h->gpu.num_cu,
+                       (hipStream_t)stream));
+    t.done();
+    return true;
+}
+
+EXPORT bool poporon_ldpc_decode_batch_device(poporon_t *h, uint8_t *d_data, size_t data_stride,
+                                             const uint8_t *d_parity, size_t parity_stride, const int8_t *d_llr,
+                                             size_t llr_stride, size_t count, uint8_t *d_ok, uint32_t *d_iterations,
+                                             uint8_t *d_hard, size_t hard_stride, void *stream)
+{
+    if (!ldpc_enter(h, "poporon_ldpc_decode_batch_device", data_stride, parity_stride, count, !d_llr))
+        return false;
+    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
+    if (count && (!d_data || !d_ok || (!d_llr && !d_parity)))
+        return fail("NULL argument");
+    if (count > 1 && ((d_llr && llr_stride < h->ldpc->codeword_bits) ||
+                      (d_hard && hard_stride < h->ldpc->codeword_bytes)))
+        return fail("llr_stride / hard_stride below the row sizes (%u / %u)", (unsigned)h->ldpc->codeword_bits,
+                    (unsigned)h->ldpc->codeword_bytes);
+    DeviceGuard dg(h->gpu.device);
+    return ldpc_launch_decode(h, d_data, data_stride, d_parity, parity_stride, d_llr, llr_stride, count, d_ok,
+                              d_iterations, d_hard, hard_stride, (hipStream_t)stream);
+}
+
+/* Host forms: chunks of rows through one pinned slot, synchronously (copy in,
+ * kernel, copy out).  `in` packs chunk [c0, c0 + n) into the slot's host
+ * buffer, `run` copies, launches and copies back on the slot's stream, `out`
+ * hands the results to the caller's arrays. */
+static const size_t kLdpcChunkBytes = (size_t)8 << 20;
+
+template <typename In, typename Run, typename Out>
+static bool ldpc_host_chunks(poporon_t *h, size_t count, size_t row_bytes, In in, Run run, Out out)
+{
+    GpuCtx::PipeSlot &ps = h->gpu.pipe[0];
+    const size_t chunk = std::max<size_t>(1, std::min(count, kLdpcChunkBytes / row_bytes));
+    if (!pipe_slot(h, ps, chunk * row_bytes + 64))
+        return false;
+    for (size_t c0 = 0; c0 < count; c0 += chunk) {
+        const size_t n = std::min(chunk, count - c0);
+        in(ps.host, c0, n);
+        const bool good = run(ps, n) && hipStreamSynchronize(ps.stream) == hipSuccess;
+        if (!good) {
+            const std::string msg =
+                g_last_error.empty() ? std::string("HIP failure in an LDPC host batch") : g_last_error;
+            (void)hipStreamSynchronize(ps.stream);
+            return fail("%s", msg.c_str());
+        }
+        out(ps.host, c0, n);
+    }
+    return true;
+}
+
+EXPORT bool poporon_ldpc_encode_batch(poporon_t *h, uint8_t *data, size_t data_stride, uint8_t *parity,
+                                      size_t parity_stride, size_t count)
+{
+    if (!ldpc_enter(h, "poporon_ldpc_encode_batch", data_stride, parity_stride, count))
+        return false;
+    BatchScope bsc{h->gpu, nullptr, true};
+    if (count && (!data || !parity))
+        return fail("NULL argument");
+    DeviceGuard dg(h->gpu.device);
+    const size_t ib = h->ldpc->info_bytes, pb = h->ldpc->parity_bytes, w = ib + pb;
+    const bool rewrites = h->ldpc->inner || h->ldpc->outer;
+    return ldpc_host_chunks(
+        h, count, w,
+        [&](uint8_t *hb, size_t c0, size_t n) { copy_rows(hb, w, data + c0 * data_stride, data_stride, ib, n); },
+        [&](GpuCtx::PipeSlot &ps, size_t n) {
+            HIP_OK(hipMemcpyAsync(ps.dev, ps.host, n * w, hipMemcpyHostToDevice, ps.stream));
+            KernelTimer t(h->gpu, POPORON_AMD_KERNEL_LDPC_ENCODE, ps.stream);
+            HIP_OK(ldpck_encode(&h->ldev, ps.dev, w, ps.dev + ib, w, n, h->gpu.num_cu, ps.stream));
+            t.done();
+            HIP_OK(hipMemcpyAsync(ps.host, ps.dev, n * w, hipMemcpyDeviceToHost, ps.stream));
+            return true;
+        },
+        [&](const uint8_t *hb, size_t c0, size_t n) {
+            if (rewrites)
+                copy_rows(data + c0 * data_stride, data_stride, hb, w, ib, n);
+            copy_rows(parity + c0 * parity_stride, parity_stride, hb + ib, w, pb, n);
+        });
+}
+
+EXPORT bool poporon_ldpc_check_batch(poporon_t *h, const uint8_t *data, size_t data_stride, const uint8_t *parity,
+                                     size_t parity_stride, size_t count, uint8_t *dirty)
+{
+    if (!ldpc_enter(h, "poporon_ldpc_check_batch", data_stride, parity_stride, count))
+        return false;
+    BatchScope bsc{h->gpu, nullptr, true};
+    if (count && (!data || !parity || !dirty))
+        return fail("NULL argument");
+    DeviceGuard dg(h->gpu.device);
+    const size_t ib = h->ldpc->info_bytes, pb = h->ldpc->parity_bytes, w = ib + pb;
+    return ldpc_host_chunks(
+        h, count, w + 1,
+        [&](uint8_t *hb, size_t c0, size_t n) {
+            copy_rows(hb, w, data + c0 * data_stride, data_stride, ib, n);
+            copy_rows(hb + ib, w, parity + c0 * parity_stride, parity_stride, pb, n);
+        },
+        [&](GpuCtx::PipeSlot &ps, size_t n) {
+            HIP_OK(hipMemcpyAsync(ps.dev, ps.host, n * w, hipMemcpyHostToDevice, ps.stream));
+            KernelTimer t(h->gpu, POPORON_AMD_KERNEL_LDPC_CHECK, ps.stream);
+            HIP_OK(ldpck_check(&h->ldev, ps.dev, w, ps.dev + ib, w, n, ps.dev + n * w, h->gpu.num_cu, ps.stream));
+            t.done();
+            HIP_OK(hipMemcpyAsync(ps.host + n * w, ps.dev + n * w, n, hipMemcpyDeviceToHost, ps.stream));
+            return true;
+        },
+        [&](const uint8_t *hb, size_t c0, size_t n) { memcpy(dirty + c0, hb + n * w, n); });
+}
+
+EXPORT bool poporon_ldpc_decode_batch(poporon_t *h, uint8_t *data, size_t data_stride, const uint8_t *parity,
+                                      size_t parity_stride, const int8_t *llr, size_t llr_stride, size_t count,
+                                      uint8_t *ok, uint32_t *iterations, uint8_t *hard, size_t hard_stride)
+{
+    if (!ldpc_enter(h, "poporon_ldpc_decode_batch", data_stride, parity_stride, count, !llr))
+        return false;
+    BatchScope bsc{h->gpu, nullptr, true};
+    if (count && (!data || !ok || (!llr && !parity)))
+        return fail("NULL argument");
+    DeviceGuard dg(h->gpu.device);
+    const size_t ib = h->ldpc->info_bytes, pb = h->ldpc->parity_bytes, w = ib + pb;
+    const size_t lb = llr ? h->ldpc->codeword_bits : 0, hb_ = hard ? h->ldpc->codeword_bytes : 0;
+    if (count > 1 && ((llr && llr_stride < lb) || (hard && hard_stride < hb_)))
+        return fail("llr_stride / hard_stride below the row sizes (%u / %u)", (unsigned)h->ldpc->codeword_bits,
+                    (unsigned)h->ldpc->codeword_bytes);
+    /* slot layout for n rows: [rows w n | llr lb n | hard hb n | iterations 4 n (4-aligned) | ok n] */
+    auto o_hard = [&](size_t n) { return n * (w + lb); };
+    auto o_it = [&](size_t n) { return (n * (w + lb + hb_) + 3) & ~(size_t)3; };
+    auto o_ok = [&](size_t n) { return o_it(n) + 4 * n; };
+    return ldpc_host_chunks(
+        h, count, w + lb + hb_ + 5 + 4,
+        [&](uint8_t *hb, size_t c0, size_t n) {
+            copy_rows(hb, w, data + c0 * data_stride, data_stride, ib, n);
+            if (parity)
+                copy_rows(hb + ib, w, parity + c0 * parity_stride, parity_stride, pb, n);
+            if (llr)
+                copy_rows(hb + n * w, lb, (const uint8_t *)llr + c0 * llr_stride, llr_stride, lb, n);
+        },
+        [&](GpuCtx::PipeSlot &ps, size_t n) {
+            HIP_OK(hipMemcpyAsync(ps.dev, ps.host, n * (w + lb), hipMemcpyHostToDevice, ps.stream));
+            if (!ldpc_launch_decode(h, ps.dev, w, ps.dev + ib, w, llr ? (const int8_t *)(ps.dev + n * w) : nullptr, lb,
+                                    n, ps.dev + o_ok(n), (uint32_t *)(ps.dev + o_it(n)),
+                                    hard ? ps.dev + o_hard(n) : nullptr, hb_, ps.stream))
+                return false;
+            HIP_OK(hipMemcpyAsync(ps.host, ps.dev, n * w, hipMemcpyDeviceToHost, ps.stream));
+            HIP_OK(hipMemcpyAsync(ps.host + o_hard(n), ps.dev + o_hard(n), o_ok(n) + n - o_hard(n),
+                                  hipMemcpyDeviceToHost, ps.stream));
+            return true;
+        },
+        [&](const uint8_t *hb, size_t c0, size_t n) {
+            copy_rows(data + c0 * data_stride, data_stride, hb, w, ib, n); /* failed rows come back unchanged */
+            if (hard)
+                copy_rows(hard + c0 * hard_stride, hard_stride, hb + o_hard(n), hb_, hb_, n);
+            if (iterations)
+                memcpy(iterations + c0, hb + o_it(n), 4 * n);
+            memcpy(ok + c0, hb + o_ok(n), n);
+        });
+}
+
+/* ------------------------------------------------------------------------ */
 /* multi-GPU: one handle per device, contiguous codeword ranges             */
 /* ------------------------------------------------------------------------ */
 
@@ -2208,6 +2640,10 @@ EXPORT poporon_multi_t *poporon_amd_multi_create(const poporon_config_t *config,
 {
     if (!config)
         return nullptr;
+    if (config->fec_type != PPLN_FEC_RS && config->fec_type != PPLN_FEC_BCH) {
+        fail("the multi-GPU handle serves RS and BCH configs");
+        return nullptr;
+    }
     std::vector<int> devs;
     if (devices) {
         devs.assign(devices, devices + num_devices);
@@ -2574,6 +3010,11 @@ EXPORT bool poporon_encode(poporon_t *h, uint8_t *data, size_t size, uint8_t *pa
         return false;
     if (h->fec_type == PPLN_FEC_BCH && size < h->bch.dbytes) /* src/encode.c:210-212 */
         return false;
+    if (h->fec_type == PPLN_FEC_LDPC) { /* src/encode.c:147-197: the host batch of one */
+        if (size != h->ldpc->info_bytes)
+            return fail("LDPC encode size %zu != info bytes %u", size, (unsigned)h->ldpc->info_bytes);
+        return poporon_ldpc_encode_batch(h, data, size, parity, h->ldpc->parity_bytes, 1);
+    }
     if (h->fec_type != PPLN_FEC_RS && h->fec_type != PPLN_FEC_BCH)
         return false;
     if (size > 65535) /* the reference's uint16 counter loops forever here (quirk Q7) */
@@ -2866,6 +3307,24 @@ EXPORT bool poporon_decode(poporon_t *h, uint8_t *data, size_t size, uint8_t *pa
         return false;
     if (h->fec_type == PPLN_FEC_BCH)
         return bch_decode_one(h, data, size, parity, corrected_num);
+    if (h->fec_type == PPLN_FEC_LDPC) {
+        /* src/decode.c:489-540: soft when the config asks for it and brought LLRs;
+         * corrected_num is the iteration count, written on success only */
+        if (size != h->ldpc->info_bytes)
+            return fail("LDPC decode size %zu != info bytes %u", size, (unsigned)h->ldpc->info_bytes);
+        const int8_t *llr = h->ldpc_soft ? h->ldpc_llr : nullptr;
+        uint8_t ok = 0;
+        uint32_t it = 0;
+        if (!poporon_ldpc_decode_batch(h, data, size, parity, h->ldpc->parity_bytes, llr, h->ldpc->codeword_bits, 1,
+                                       &ok, &it, nullptr, 0))
+            return false;
+        h->ldpc_last_iterations = it;
+        if (!ok)
+            return false;
+        if (corrected_num)
+            *corrected_num = it;
+        return true;
+    }
     if (h->fec_type != PPLN_FEC_RS)
         return false;
     size_t fixed = 0;
