@@ -1353,7 +1353,7 @@ static bool ensure_stage(poporon_t *h, size_t bytes)
 /* LDPC decode: messages in LDS (the forced or automatic choice), else in the workspace */
 static bool ldpc_use_lds(const poporon_t *h)
 {
-    return h->ldpc_path == 1 || (h->ldpc_path == 0 && ldpck_decode_lds_bytes(&h->ldev) <= LDPC_LDS_MAX);
+    return h->ldpc_path == 1 || (h->ldpc_path == 0 && ldpck_decode_lds_bytes(&h->ldev) <= ldpck_decode_lds_room());
 }
 
 /* the workspace of a decode of `count` rows: one slice per workgroup of its launch */
@@ -2400,9 +2400,10 @@ static bool ldpc_launch_decode(poporon_t *h, uint8_t *d_data, size_t ds, const u
     if (count == 0)
         return true;
     const bool lds = ldpc_use_lds(h);
-    if (lds && ldpck_decode_lds_bytes(&h->ldev) > LDPC_LDS_MAX)
-        return fail("POPORON_AMD_LDPC_PATH=lds: the code's messages (%zu bytes) do not fit the CU's %u bytes of LDS",
-                    ldpck_decode_lds_bytes(&h->ldev), (unsigned)LDPC_LDS_MAX);
+    if (lds && ldpck_decode_lds_bytes(&h->ldev) > ldpck_decode_lds_room())
+        return fail("POPORON_AMD_LDPC_PATH=lds: the code's messages (%zu bytes) do not fit the %zu bytes the kernel "
+                    "leaves of the CU's %u bytes of LDS",
+                    ldpck_decode_lds_bytes(&h->ldev), ldpck_decode_lds_room(), (unsigned)LDPC_LDS_MAX);
     const uint32_t grid = ldpck_decode_grid(&h->ldev, count, g.num_cu, lds);
     if (!lds && (!ldpc_reserve(h, count) || !rem_acquire(g, s)))
         return false;

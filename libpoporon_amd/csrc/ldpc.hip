@@ -339,6 +339,21 @@ static size_t cw_lds(const LdpcDev *prm) { return ((size_t)prm->codeword_bytes +
 extern "C" size_t ldpck_decode_lds_bytes(const LdpcDev *prm) { return msg_bytes(*prm) + cw_lds(prm); }
 extern "C" size_t ldpck_slice_bytes(const LdpcDev *prm) { return msg_bytes(*prm); }
 
+/* LDS the compiler gives ldpc_decode_k<true> on its own (__syncthreads_or keeps words there):
+ * it comes out of the same 160 KiB as the dynamic bytes.  Nothing fits where it cannot be read. */
+static size_t decode_static_lds()
+{
+    static const size_t bytes = [] {
+        hipFuncAttributes a;
+        if (hipFuncGetAttributes(&a, reinterpret_cast<const void *>(ldpc_decode_k<true>)) != hipSuccess)
+            return (size_t)LDPC_LDS_MAX;
+        return (size_t)a.sharedSizeBytes;
+    }();
+    return bytes;
+}
+
+extern "C" size_t ldpck_decode_lds_room(void) { return LDPC_LDS_MAX - std::min<size_t>(LDPC_LDS_MAX, decode_static_lds()); }
+
 static uint32_t rows_grid(size_t count, size_t cap)
 {
     return (uint32_t)std::max<size_t>(1, std::min(count, std::max<size_t>(cap, 1)));
@@ -395,7 +410,7 @@ extern "C" hipError_t ldpck_decode(const LdpcDev *prm, uint8_t *data, size_t dst
         max_iterations = 50; /* src/ldpc.c:981-983 */
     if (lds) {
         const size_t bytes = ldpck_decode_lds_bytes(prm);
-        if (bytes > LDPC_LDS_MAX)
+        if (bytes > ldpck_decode_lds_room())
             return hipErrorInvalidValue;
         const hipError_t e = allow_lds(ldpc_decode_k<true>, bytes);
         if (e != hipSuccess)

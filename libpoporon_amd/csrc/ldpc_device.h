@@ -30,6 +30,9 @@ extern "C" {
  * one workgroup's slice of the global workspace otherwise */
 size_t ldpck_decode_lds_bytes(const LdpcDev *prm);
 size_t ldpck_slice_bytes(const LdpcDev *prm);
+/* the dynamic LDS a decode workgroup can get: LDPC_LDS_MAX less the kernel's static LDS
+ * (needs the device: call with the handle's device current) */
+size_t ldpck_decode_lds_room(void);
 /* workgroups of a decode launch (each takes rows blockIdx.x, + gridDim.x, ...) */
 uint32_t ldpck_decode_grid(const LdpcDev *prm, size_t count, int num_cu, bool lds);
 

@@ -1,6 +1,7 @@
 """Shared by the LDPC tests and tools/gen_golden_ldpc.py (not a test module).
 
 * CODES: the test codes A-H (+ M, a code whose messages need more than 64 KiB of LDS).
+* SWEEP: the edge-shaped codes of tests/test_gpu_ldpc_sweep.py and their seeded rows.
 * Seeded inputs (numpy Generators).  The golden file records the SHA-256 of
   every input array next to the reference's outputs, so a numpy whose streams
   differ fails loudly instead of comparing against the wrong rows.
@@ -46,6 +47,125 @@ SIGMAS = (0.5, 0.8, 1.0)
 SOFT_EXTRA = 16
 SENT = 777
 
+# The sweep codes (tests/golden/ldpc_sweep_golden.npz, tools/gen_golden_ldpc_sweep.py): shapes at
+# which ldpc.hip takes paths of its own.  "depth" is poporon_ldpc_config_create's interleave_depth.
+SWEEP_GOLDEN = os.path.join(ROOT, "tests", "golden", "ldpc_sweep_golden.npz")
+SWEEP = {
+    # inner interleaver with spare bits in parity and codeword (341 bits); a seed past 2^32
+    "S1": dict(block=32, rate=3, matrix=RANDOM, weight=3, outer=True, inner=True, depth=11, lifting=0,
+               seed=(1 << 32) + 17),
+    # the same with QC; 117 check rows: one full wave and a partial one
+    "S2": dict(block=44, rate=3, matrix=QC, weight=4, outer=False, inner=True, depth=7, lifting=0, seed=2),
+    # fewer than 64 check rows; row degree up to 41
+    "S3": dict(block=36, rate=5, matrix=RANDOM, weight=5, outer=True, inner=True, depth=15, lifting=0, seed=3),
+    # 260 parity bytes: encode's prefix pass has runs of 2 bytes, lanes 130-255 empty
+    "S4": dict(block=260, rate=1, matrix=RANDOM, weight=4, outer=True, inner=True, depth=65, lifting=0, seed=4),
+    # weight 8; 512 check rows: two full passes of the encode loop
+    "S5": dict(block=32, rate=0, matrix=RANDOM, weight=8, outer=False, inner=False, depth=0, lifting=0, seed=5),
+    # a lifting factor that is no power of two, 4 x 24 > 80 check rows: edges are dropped
+    "S6": dict(block=40, rate=4, matrix=QC, weight=3, outer=True, inner=False, depth=0, lifting=24, seed=6),
+    # decode LDS 65,184 B (the last size that needs no attribute), 65,968 B (the first that does),
+    # 163,744 B (96 B under LDPC_LDS_MAX, yet past what the kernel's static LDS leaves of it: the
+    # workspace) and 164,512 B (past LDPC_LDS_MAX: the workspace)
+    "W336": dict(block=336, rate=1, matrix=RANDOM, weight=3, outer=False, inner=False, depth=0, lifting=0, seed=7),
+    "W340": dict(block=340, rate=1, matrix=RANDOM, weight=3, outer=False, inner=False, depth=0, lifting=0, seed=42),
+    "W844": dict(block=844, rate=1, matrix=RANDOM, weight=3, outer=False, inner=False, depth=0, lifting=0, seed=9),
+    # seed 30: a check row with a single edge
+    "W848": dict(block=848, rate=1, matrix=RANDOM, weight=3, outer=True, inner=False, depth=0, lifting=0, seed=30),
+    # 162,960 B: the largest block of this family whose messages do fit the LDS
+    "W840": dict(block=840, rate=1, matrix=RANDOM, weight=3, outer=False, inner=False, depth=0, lifting=0, seed=10),
+}
+# W340 with the automatic inner depth: the table is no permutation, the handle is not served
+SWEEP_REFUSED = dict(SWEEP["W340"], inner=True)
+SWEEP_SEED = 0x53574550
+SWEEP_SOFT_ROWS = 22
+
+
+def sweep_large(code):
+    return code["block"] > 200
+
+
+def sweep_enc_inputs(name):
+    code = SWEEP[name]
+    rng = np.random.default_rng([SWEEP_SEED, list(SWEEP).index(name), 1])
+    return rng.integers(0, 256, (12 if sweep_large(code) else 48, code["block"]), dtype=np.uint8)
+
+
+def sweep_flip_one(name, enc_data, enc_parity, codeword_bits):
+    """Every encoded row with one bit of the codeword flipped."""
+    rng = np.random.default_rng([SWEEP_SEED, list(SWEEP).index(name), 2])
+    bits = rng.integers(0, codeword_bits, enc_data.shape[0])
+    row = np.concatenate([enc_data, enc_parity], axis=1)
+    row[np.arange(len(row)), bits // 8] ^= (0x80 >> (bits % 8)).astype(np.uint8)
+    ib = enc_data.shape[1]
+    return np.ascontiguousarray(row[:, :ib]), np.ascontiguousarray(row[:, ib:])
+
+
+def sweep_hard_rows(name, enc_data, enc_parity, seed=4):
+    """flip_rows with the sweep's flip counts: 0, 1, 3, 8, 30 x 16 rows, or 0, 2, 20, 300 x 4 for
+    the large blocks."""
+    code = SWEEP[name]
+    flips, per = ((0, 2, 20, 300), 4) if sweep_large(code) else ((0, 1, 3, 8, 30), 16)
+    rng_seed = int(np.random.default_rng([SWEEP_SEED, list(SWEEP).index(name), seed]).integers(1 << 62))
+    return flip_rows(enc_data, enc_parity, flips=flips, per=per, seed=rng_seed)
+
+
+def sweep_soft_rows(name, enc_data, enc_parity, codeword_bits, seed=5):
+    """22 LLR rows in channel order that reach the saturated regime (|llr| >= 126 gives
+    |llr * 256| > 32000), and junk data / parity the soft path must not read:
+      12  codeword signs at magnitude 127, 16 and 1, four rows each, 4 % of the positions negated
+       4  codeword signs at 127, 3 % of the positions set to -128 or 0
+       1  all 0;  1  all -128;  1  all 127
+       3  drawn from {-128, -127, 127}"""
+    rng = np.random.default_rng([SWEEP_SEED, list(SWEEP).index(name), seed])
+    bits = np.unpackbits(np.concatenate([enc_data, enc_parity], axis=1), axis=1)[:, :codeword_bits].astype(np.int64)
+    sign = 1 - 2 * bits[rng.integers(0, enc_data.shape[0], 16)]
+    out = []
+    for k, mag in enumerate((127, 16, 1)):
+        s = sign[4 * k:4 * k + 4] * mag
+        out.append(np.where(rng.random(s.shape) < 0.04, -s, s))
+    s = sign[12:16] * 127
+    hit = rng.random(s.shape) < 0.03
+    out.append(np.where(hit, np.where(rng.random(s.shape) < 0.5, -128, 0), s))
+    for v in (0, -128, 127):
+        out.append(np.full((1, codeword_bits), v, np.int64))
+    out.append(np.array([-128, -127, 127])[rng.integers(0, 3, (3, codeword_bits))])
+    llr = np.ascontiguousarray(np.concatenate(out).astype(np.int8))
+    assert llr.shape[0] == SWEEP_SOFT_ROWS
+    junk_d = rng.integers(0, 256, (llr.shape[0], enc_data.shape[1]), dtype=np.uint8)
+    junk_p = rng.integers(0, 256, (llr.shape[0], enc_parity.shape[1]), dtype=np.uint8)
+    return llr, junk_d, junk_p
+
+
+SINGLE_EDGE_LLR = (-117, -118, -119, -120, -125, -128)
+
+
+def sweep_single_edge_rows(graph):
+    """LLR rows in channel order for a graph (row_ptr, col_idx, inner_forward) with a check row of
+    one edge.  Such a row has no second minimum: its edge gets the start value of the minima,
+    32000 * 15 / 16 = +30000, every iteration.  The bit on that edge is given an LLR whose channel
+    term, llr * 256, lies within a few hundred of -30000, every other bit 0 (and, in a second set,
+    +1), so the sign of that bit's total is the sign of channel + 30000: a start value that is off
+    by a little changes the hard decision."""
+    row_ptr = np.asarray(graph["row_ptr"], dtype=np.int64)
+    rows = np.nonzero(np.diff(row_ptr) == 1)[0]
+    assert rows.size, "no check row with a single edge"
+    bit = int(graph["col_idx"][row_ptr[rows[0]]])
+    n = int(graph["num_bits"])
+    pos = bit if graph["inner_forward"] is None else int(graph["inner_forward"][bit])
+    llr = np.zeros((2 * len(SINGLE_EDGE_LLR), n), np.int8)
+    llr[len(SINGLE_EDGE_LLR):] = 1
+    llr[:, pos] = SINGLE_EDGE_LLR * 2
+    return llr
+
+
+def decode_lds_bytes(num_edges, num_bits):
+    """Dynamic LDS of ldpc_decode_k<true>: three int16 arrays (two per edge, one per bit) and the
+    row's byte image, each rounded up to 16 bytes."""
+    r16 = lambda v: (v + 15) & ~15  # noqa: E731
+    return r16(2 * (2 * num_edges + num_bits)) + r16((num_bits + 7) // 8)
+
+
 _NUM = {0: (1, 2), 1: (1, 1), 2: (2, 1), 3: (3, 1), 4: (4, 1), 5: (5, 1)}
 
 
@@ -62,8 +182,8 @@ def sha(a) -> str:
 
 def config_args(code, max_iterations=MAX_ITER, soft=False, llr_ptr=None, llr_size=0):
     """poporon_ldpc_config_create's 13 arguments."""
-    return (code["block"], code["rate"], code["matrix"], code["weight"], soft, code["outer"], code["inner"], 0,
-            code["lifting"], max_iterations, llr_ptr, llr_size, code["seed"])
+    return (code["block"], code["rate"], code["matrix"], code["weight"], soft, code["outer"], code["inner"],
+            code.get("depth", 0), code["lifting"], max_iterations, llr_ptr, llr_size, code["seed"])
 
 
 # ---- seeded inputs ---------------------------------------------------------------------
