@@ -138,6 +138,49 @@ bool poporon_decode_batch(poporon_t *pprn, uint8_t *data, size_t data_stride, ui
                           size_t size, size_t count, const uint8_t *positions, size_t positions_stride,
                           const uint8_t *counts, uint8_t *ok, uint8_t *corrected);
 
+/* ---- symbol-interleaved RS frames ---------------------------------------------
+ * RS(255,223) data usually arrives interleaved (CCSDS 131.0-B transfer frames,
+ * depths 1, 2, 3, 4, 5 and 8): frame f holds `depth` codewords, symbol by
+ * symbol.  Its message region is size*depth bytes at d_data + f*data_stride,
+ * message symbol j of codeword i at offset j*depth + i; its parity region
+ * num_roots*depth bytes at d_parity + f*parity_stride, parity symbol p of
+ * codeword i at offset p*depth + i.  The CCSDS wire block is d_parity =
+ * d_data + size*depth with both strides (size + num_roots)*depth; any other
+ * placement, base alignment or stride (>= the region) is as valid, and bytes
+ * of a stride past a region are never written.  count is the number of
+ * frames, 1 <= depth <= 64, depth 1 is the row layout, RS handles only.
+ *
+ * Codeword c = f*depth + i indexes every per-codeword array: d_ok[c],
+ * d_corrected[c], d_dirty[c], d_counts[c], d_positions[c*positions_stride ..];
+ * erasure positions are symbol indices into the codeword's own message, as in
+ * the row call.  Every per-codeword result equals the row call's on the
+ * de-interleaved codeword: the frames of a chunk are gathered into rows in a
+ * staging buffer the handle owns (256 B per codeword), the row kernels run
+ * there, and parity (encode) or both regions (decode) are scattered back.  A
+ * chunk is at most 2^20 codewords (POPORON_AMD_ILV_CHUNK=<codewords> in the
+ * environment at poporon_create; whole frames, at least one); larger batches
+ * run chunk after chunk on `stream`.  poporon_amd_reserve_interleaved sizes
+ * the staging for min(max_codewords, chunk) codewords and does for that count
+ * what poporon_amd_reserve does, so that later device calls allocate nothing.
+ * The host forms move chunks of frames through pinned memory and return when
+ * the results are in host memory. */
+bool poporon_encode_interleaved_device(poporon_t *pprn, const uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                       size_t parity_stride, size_t size, size_t depth, size_t count, void *stream);
+bool poporon_decode_interleaved_device(poporon_t *pprn, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                       size_t parity_stride, size_t size, size_t depth, size_t count,
+                                       const uint8_t *d_positions, size_t positions_stride, const uint8_t *d_counts,
+                                       uint8_t *d_ok, uint8_t *d_corrected, void *stream);
+bool poporon_check_interleaved_device(poporon_t *pprn, const uint8_t *d_data, size_t data_stride,
+                                      const uint8_t *d_parity, size_t parity_stride, size_t size, size_t depth,
+                                      size_t count, uint8_t *d_dirty, void *stream);
+bool poporon_encode_interleaved(poporon_t *pprn, const uint8_t *data, size_t data_stride, uint8_t *parity,
+                                size_t parity_stride, size_t size, size_t depth, size_t count);
+bool poporon_decode_interleaved(poporon_t *pprn, uint8_t *data, size_t data_stride, uint8_t *parity,
+                                size_t parity_stride, size_t size, size_t depth, size_t count,
+                                const uint8_t *positions, size_t positions_stride, const uint8_t *counts, uint8_t *ok,
+                                uint8_t *corrected);
+bool poporon_amd_reserve_interleaved(poporon_t *pprn, size_t max_codewords);
+
 /* ---- LDPC batches -----------------------------------------------------------
  * Row c has info_bytes (poporon_get_info_size) of data at d_data +
  * c*data_stride and parity_bytes (poporon_get_parity_size) of parity at
@@ -218,6 +261,10 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
  * the one-codeword-per-wave decoder (rs_wave_k, syndromes included).
  * LDPC handles: 12 = encode (ldpc_encode_k), 13 = decode (ldpc_decode_k),
  * 14 = check (ldpc_check_k).
+ * The interleaved calls at depth > 1: 15 = frames to staging rows
+ * (rs_ilv_gather_k), 16 = rows back to frames (rs_ilv_scatter_k), one launch
+ * each per chunk; the codec kernels between them keep their ids, routed by the
+ * chunk's codeword count.
  *
  * Error- and erasure-mode batches of at least 16384 codewords take the split
  * decode; POPORON_AMD_DECODE_PATH=split / single / wave in the environment
@@ -238,6 +285,8 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
 #define POPORON_AMD_KERNEL_LDPC_ENCODE 12
 #define POPORON_AMD_KERNEL_LDPC_DECODE 13
 #define POPORON_AMD_KERNEL_LDPC_CHECK 14
+#define POPORON_AMD_KERNEL_ILV_GATHER 15
+#define POPORON_AMD_KERNEL_ILV_SCATTER 16
 bool poporon_amd_timing(poporon_t *pprn, int enable);
 bool poporon_amd_timing_read(poporon_t *pprn, int kernel, double *total_ms, uint64_t *launches);
 

@@ -86,6 +86,17 @@ _SIGS = {
     "poporon_encode_batch": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t]),
     "poporon_decode_batch": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp,
                                         C.c_size_t, _vp, _vp, _vp]),
+    "poporon_encode_interleaved_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                     C.c_size_t, _vp]),
+    "poporon_decode_interleaved_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                     C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "poporon_check_interleaved_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                    C.c_size_t, _vp, _vp]),
+    "poporon_encode_interleaved": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                              C.c_size_t]),
+    "poporon_decode_interleaved": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                              C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "poporon_amd_reserve_interleaved": (C.c_bool, [_vp, C.c_size_t]),
     "poporon_rng_create": (_vp, [C.c_int, _vp, C.c_size_t]),
     "poporon_rng_destroy": (None, [_vp]),
     "poporon_rng_next": (C.c_bool, [_vp, _vp, C.c_size_t]),
@@ -122,12 +133,15 @@ KERNEL_ENCODE, KERNEL_REMAINDER, KERNEL_CORRECT = 0, 1, 2
 KERNEL_BM, KERNEL_CHIEN, KERNEL_FORNEY, KERNEL_LIST, KERNEL_APPLY, KERNEL_ERASURE, KERNEL_SINGLE = 4, 5, 6, 7, 8, 9, 10
 KERNEL_WAVE = 11
 KERNEL_LDPC_ENCODE, KERNEL_LDPC_DECODE, KERNEL_LDPC_CHECK = 12, 13, 14
+KERNEL_ILV_GATHER, KERNEL_ILV_SCATTER = 15, 16
 KERNEL_NAMES = {KERNEL_ENCODE: "rs_lfsr_k<false> (encode)", KERNEL_REMAINDER: "rs_lfsr_k<true> (remainder)",
                 KERNEL_CORRECT: "rs_correct_k (BM/Chien/Forney)", KERNEL_BM: "rs_bm_k (BM/Omega)",
                 KERNEL_CHIEN: "rs_chien_k (Chien)", KERNEL_FORNEY: "rs_forney_k (Forney)",
                 KERNEL_APPLY: "rs_apply_k (apply)", KERNEL_LIST: "rs_wave_k (list)",
                 KERNEL_ERASURE: "rs_era_bp_k (erasure)", KERNEL_SINGLE: "rs_dec1_k (one codeword)",
                 KERNEL_WAVE: "rs_wave_k (small batch)"}
+ILV_KERNEL_NAMES = {KERNEL_ILV_GATHER: "rs_ilv_gather_k (frames to rows)",
+                    KERNEL_ILV_SCATTER: "rs_ilv_scatter_k (rows to frames)"}
 LDPC_KERNEL_NAMES = {KERNEL_LDPC_ENCODE: "ldpc_encode_k", KERNEL_LDPC_DECODE: "ldpc_decode_k",
                      KERNEL_LDPC_CHECK: "ldpc_check_k"}
 
@@ -370,6 +384,63 @@ class Poporon:
 
     def reserve(self, max_count):
         self._check(self.lib.poporon_amd_reserve(self.h, max_count), "poporon_amd_reserve")
+
+    # ---- symbol-interleaved frames (include/poporon_amd.h) --------------------------
+    # frame f: message symbol j of codeword i at d_data + f*data_stride + j*depth + i, parity symbol p at
+    # d_parity + f*parity_stride + p*depth + i; count frames; per-codeword arrays indexed by f*depth + i
+    def encode_interleaved_device(self, d_data, data_stride, d_parity, parity_stride, size, depth, count, stream=0):
+        self._check(self.lib.poporon_encode_interleaved_device(self.h, d_data, data_stride, d_parity, parity_stride,
+                                                               size, depth, count, stream or None),
+                    "poporon_encode_interleaved_device")
+
+    def decode_interleaved_device(self, d_data, data_stride, d_parity, parity_stride, size, depth, count, d_ok,
+                                  d_corrected=None, d_positions=None, positions_stride=0, d_counts=None, stream=0):
+        self._check(self.lib.poporon_decode_interleaved_device(self.h, d_data, data_stride, d_parity, parity_stride,
+                                                               size, depth, count, d_positions, positions_stride,
+                                                               d_counts, d_ok, d_corrected, stream or None),
+                    "poporon_decode_interleaved_device")
+
+    def check_interleaved_device(self, d_data, data_stride, d_parity, parity_stride, size, depth, count, d_dirty,
+                                 stream=0):
+        self._check(self.lib.poporon_check_interleaved_device(self.h, d_data, data_stride, d_parity, parity_stride,
+                                                              size, depth, count, d_dirty, stream or None),
+                    "poporon_check_interleaved_device")
+
+    def reserve_interleaved(self, max_codewords):
+        self._check(self.lib.poporon_amd_reserve_interleaved(self.h, max_codewords),
+                    "poporon_amd_reserve_interleaved")
+
+    def encode_interleaved(self, frames, depth):
+        """frames u8[count, size*depth] (message regions) -> parity regions u8[count, num_roots*depth]."""
+        fr = np.ascontiguousarray(frames, dtype=np.uint8)
+        count, width = fr.shape
+        if depth < 1 or width % depth:
+            raise PoporonError(f"frame width {width} is no multiple of depth {depth}")
+        par = np.zeros((count, self.num_roots * depth), np.uint8)
+        self._check(self.lib.poporon_encode_interleaved(self.h, _buf(fr), width, _buf(par), par.shape[1],
+                                                        width // depth, depth, count), "poporon_encode_interleaved")
+        return par
+
+    def decode_interleaved(self, frames, parity, depth, positions=None, counts=None):
+        """Returns (ok u8[count*depth], corrected u8[count*depth], frames', parity'); positions
+        u8[count*depth, >= num_roots] and counts u8[count*depth] select the erasure decode."""
+        d = np.array(frames, dtype=np.uint8, copy=True, order="C")
+        p = np.array(parity, dtype=np.uint8, copy=True, order="C")
+        count, width = d.shape
+        if depth < 1 or width % depth:
+            raise PoporonError(f"frame width {width} is no multiple of depth {depth}")
+        ok = np.zeros(count * depth, np.uint8)
+        cor = np.zeros(count * depth, np.uint8)
+        if positions is not None:
+            pos = np.ascontiguousarray(positions, dtype=np.uint8)
+            cnt = np.ascontiguousarray(counts, dtype=np.uint8)
+            pargs = (_buf(pos), pos.shape[1], _buf(cnt))
+        else:
+            pargs = (None, 0, None)
+        self._check(self.lib.poporon_decode_interleaved(self.h, _buf(d), width, _buf(p), p.shape[1], width // depth,
+                                                        depth, count, *pargs, _buf(ok), _buf(cor)),
+                    "poporon_decode_interleaved")
+        return ok, cor, d, p
 
     # ---- in-library kernel timing (HIP events on the launch stream) ---------------
     def timing(self, enable: bool):

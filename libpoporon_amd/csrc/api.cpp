@@ -118,7 +118,7 @@ struct _poporon_config_t {
     uint64_t seed;
 };
 
-#define NKERN 15
+#define NKERN 17
 struct TimedLaunch {
     int kernel;
     hipEvent_t a, b;
@@ -141,6 +141,10 @@ struct GpuCtx {
     uint8_t *lws = nullptr;     /* device (LDPC): messages of the decode kernel's workgroups, lws_bytes */
     size_t lws_bytes = 0;
     size_t rem_cap = 0;
+    /* staging rows of the interleaved calls (rs_interleave.hip), RS_ILV_ROW
+     * bytes per codeword; shared across streams under rem's ordering */
+    uint8_t *ilv = nullptr;
+    size_t ilv_cap = 0;
     /* Ordering of the workspace across streams: rem_done is recorded on the
      * stream of the last launch that read rem (rem_stream); a call on another
      * stream waits for it before overwriting rem. */
@@ -184,6 +188,10 @@ struct GpuCtx {
 };
 #define PIPE_SLOTS 3
 
+/* interleaved calls: codewords staged at a time (256 B each), default and the cap of the override */
+#define ILV_CHUNK_DEFAULT ((size_t)1 << 20)
+#define ILV_CHUNK_MAX (1ull << 24)
+
 struct _poporon_t {
     poporon_fec_type_t fec_type;
     poporon_rs_t *rs;
@@ -201,6 +209,7 @@ struct _poporon_t {
     bool generic;   /* served by the general-parameter kernels (rs_generic.hip) */
     bool lfsr_nr;   /* generic code, num_roots <= 32: batch encodes on the LFSR kernel (rsk_encode_nr) */
     bool nrsplit;   /* ... and large error-mode batches decode on the split kernels (params_nrsplit) */
+    size_t ilv_chunk; /* codewords the interleaved calls stage at a time (POPORON_AMD_ILV_CHUNK) */
     int gen_path;   /* general kernels: 0 by batch size, 1 one codeword per lane (rsg_*), 2 one per wave
                        (rsgw_*); POPORON_AMD_GENERIC=lane|wave */
     RsDevTables host_tab;
@@ -933,6 +942,11 @@ EXPORT poporon_t *poporon_create(const poporon_config_t *config)
         const char *gp = getenv("POPORON_AMD_GENERIC");
         h->gen_path = !gp ? 0 : !strcmp(gp, "lane") ? 1 : !strcmp(gp, "wave") ? 2 : 0;
     }
+    {
+        const char *ic = getenv("POPORON_AMD_ILV_CHUNK");
+        const unsigned long long v = ic ? strtoull(ic, nullptr, 10) : 0ull;
+        h->ilv_chunk = v ? (size_t)std::min<unsigned long long>(v, ILV_CHUNK_MAX) : ILV_CHUNK_DEFAULT;
+    }
     if (h->fast)
         build_tables(h);
     if (h->generic)
@@ -1065,7 +1079,7 @@ static void gpu_release(GpuCtx &g)
 {
     const int dev = g.device;
     const bool any = g.ready || g.stream || g.sstream || g.tab || g.gtab || g.rem || g.ltab || g.lws || g.stage ||
-                     g.hstage || g.zc ||
+                     g.hstage || g.zc || g.ilv ||
                      g.rem_done || g.registered || g.batch_ev ||
                      g.pipe[0].stream || g.pipe[1].stream || g.pipe[2].stream;
     if (!any || dev < 0) {
@@ -1094,6 +1108,7 @@ static void gpu_release(GpuCtx &g)
     (void)hipFree(g.tab);
     (void)hipFree(g.gtab);
     (void)hipFree(g.rem);
+    (void)hipFree(g.ilv);
     (void)hipFree(g.ltab);
     (void)hipFree(g.lws);
     (void)hipFree(g.stage);
@@ -1978,21 +1993,10 @@ static bool launch_decode(poporon_t *h, uint8_t *d_data, size_t ds, uint8_t *d_p
     return !shared || rem_release(h->gpu, s);
 }
 
-EXPORT bool poporon_check_batch_device(poporon_t *h, const uint8_t *d_data, size_t data_stride,
-                                       const uint8_t *d_parity, size_t parity_stride, size_t size, size_t count,
-                                       uint8_t *d_dirty, void *stream)
+/* d_dirty[c] = codeword c's syndrome is nonzero (RS handles) */
+static bool launch_check(poporon_t *h, const uint8_t *d_data, size_t data_stride, const uint8_t *d_parity,
+                         size_t parity_stride, size_t size, size_t count, uint8_t *d_dirty, hipStream_t s)
 {
-    if (!h || (count && (!d_data || !d_parity || !d_dirty)))
-        return fail("NULL argument");
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("poporon_check_batch_device serves RS handles");
-    if (!check_decode_size(h, size))
-        return fail("size %zu outside [1, %u]", size, (unsigned)kmax(h));
-    if (!batch_enter(h))
-        return false;
-    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
-    DeviceGuard dg(h->gpu.device);
-    hipStream_t s = (hipStream_t)stream;
     KernelTimer t(h->gpu, POPORON_AMD_KERNEL_CHECK, s);
     if (h->fast) {
         HIP_OK(rsk_check(h->gpu.tab, d_data, data_stride, d_parity, parity_stride, (uint32_t)size, count, d_dirty,
@@ -2012,6 +2016,23 @@ EXPORT bool poporon_check_batch_device(poporon_t *h, const uint8_t *d_data, size
     }
     t.done();
     return true;
+}
+
+EXPORT bool poporon_check_batch_device(poporon_t *h, const uint8_t *d_data, size_t data_stride,
+                                       const uint8_t *d_parity, size_t parity_stride, size_t size, size_t count,
+                                       uint8_t *d_dirty, void *stream)
+{
+    if (!h || (count && (!d_data || !d_parity || !d_dirty)))
+        return fail("NULL argument");
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("poporon_check_batch_device serves RS handles");
+    if (!check_decode_size(h, size))
+        return fail("size %zu outside [1, %u]", size, (unsigned)kmax(h));
+    if (!batch_enter(h))
+        return false;
+    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
+    DeviceGuard dg(h->gpu.device);
+    return launch_check(h, d_data, data_stride, d_parity, parity_stride, size, count, d_dirty, (hipStream_t)stream);
 }
 
 EXPORT bool poporon_syndrome_batch_device(poporon_t *h, const uint8_t *d_data, size_t data_stride,
@@ -2597,6 +2618,261 @@ EXPORT bool poporon_ldpc_decode_batch(poporon_t *h, uint8_t *data, size_t data_s
                 memcpy(iterations + c0, hb + o_it(n), 4 * n);
             memcpy(ok + c0, hb + o_ok(n), n);
         });
+}
+
+/* ------------------------------------------------------------------------ */
+/* symbol-interleaved frames: layout kernels around the row kernels         */
+/* ------------------------------------------------------------------------ */
+
+/*
+ * A frame holds `depth` codewords interleaved symbol by symbol (poporon_amd.h).
+ * The codec kernels are untouched: a chunk of frames is gathered into staging
+ * rows (rs_interleave.hip; size + num_roots bytes back to back, the wire rows
+ * the codec kernels are measured on, in RS_ILV_ROW bytes per codeword), the
+ * row launchers run there on codewords c = f*depth + i, and the results are
+ * scattered back -- the parity for an encode, both regions for a decode,
+ * nothing for a check.  Depth 1 is the row layout and runs in place.  A chunk
+ * is at most ilv_chunk codewords, in whole frames and at least one frame;
+ * larger batches run chunk after chunk on the caller's stream.  The staging
+ * buffer is the handle's, grown on demand, and shares the split workspace's
+ * ordering across streams (rem_acquire / rem_release).
+ */
+static bool ensure_ilv(poporon_t *h, size_t codewords)
+{
+    GpuCtx &g = h->gpu;
+    if (g.ilv_cap >= codewords)
+        return true;
+    const size_t cap = std::max(codewords, (size_t)RS_ILV_MAX_DEPTH);
+    if (g.ilv) {
+        if (g.rem_pending) /* its last reader may run on any stream the caller chose */
+            HIP_OK(hipEventSynchronize(g.rem_done));
+        g.rem_pending = false;
+        HIP_OK(hipFree(g.ilv));
+        g.ilv = nullptr;
+        g.ilv_cap = 0;
+    }
+    HIP_OK(hipMalloc((void **)&g.ilv, cap * RS_ILV_ROW));
+    g.ilv_cap = cap;
+    return true;
+}
+
+enum { ILV_ENCODE, ILV_DECODE, ILV_CHECK };
+
+struct IlvCall {
+    int op;
+    uint8_t *data;
+    size_t ds;
+    uint8_t *par;
+    size_t ps;
+    size_t size, depth, count; /* count: frames */
+    const uint8_t *pos;
+    size_t pos_stride;
+    const uint8_t *cnt;
+    uint8_t *ok, *cor, *dirty;
+};
+
+static size_t ilv_chunk_frames(const poporon_t *h, size_t depth) { return std::max<size_t>(1, h->ilv_chunk / depth); }
+
+/* the checks every interleaved entry point makes before it touches the GPU */
+static bool ilv_args(const poporon_t *h, const char *what, const IlvCall &c)
+{
+    if (!h)
+        return fail("%s: NULL handle", what);
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("%s serves RS handles", what);
+    if (c.count && (!c.data || !c.par || (c.op == ILV_DECODE && !c.ok) || (c.op == ILV_CHECK && !c.dirty)))
+        return fail("%s: NULL argument", what);
+    if (c.depth < 1 || c.depth > RS_ILV_MAX_DEPTH)
+        return fail("%s: depth %zu outside [1, %u]", what, c.depth, (unsigned)RS_ILV_MAX_DEPTH);
+    if (!check_decode_size(h, c.size))
+        return fail("%s: size %zu outside [1, %u]", what, c.size, (unsigned)kmax(h));
+    const size_t nr = h->rs->num_roots;
+    if (c.ds < c.size * c.depth)
+        return fail("%s: data_stride %zu < size * depth = %zu", what, c.ds, c.size * c.depth);
+    if (c.ps < nr * c.depth)
+        return fail("%s: parity_stride %zu < num_roots * depth = %zu", what, c.ps, nr * c.depth);
+    if (c.pos && (!c.cnt || c.pos_stride < nr))
+        return fail("%s: erasure batch needs counts and positions_stride >= num_roots", what);
+    return true;
+}
+
+/* device pointers; the caller holds the batch scope and the device */
+static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
+{
+    GpuCtx &g = h->gpu;
+    const uint32_t nr = h->rs->num_roots;
+    const size_t cf = ilv_chunk_frames(h, c.depth);
+    const bool staged = c.depth > 1;
+    if (staged && (!ensure_ilv(h, std::min(c.count, cf) * c.depth) || !rem_acquire(g, s)))
+        return false;
+    for (size_t f0 = 0; f0 < c.count; f0 += cf) {
+        const size_t n = std::min(cf, c.count - f0), ncw = n * c.depth, c0 = f0 * c.depth;
+        uint8_t *fd = c.data + f0 * c.ds, *fp = c.par + f0 * c.ps;
+        uint8_t *rd = staged ? g.ilv : fd, *rp = staged ? g.ilv + c.size : fp;
+        const size_t rds = staged ? c.size + nr : c.ds, rps = staged ? c.size + nr : c.ps; /* staged: wire rows */
+        if (staged) {
+            KernelTimer t(g, POPORON_AMD_KERNEL_ILV_GATHER, s);
+            HIP_OK(rsk_ilv_gather(fd, c.ds, fp, c.ps, g.ilv, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
+                                  c.op != ILV_ENCODE, s));
+            t.done();
+        }
+        if (c.op == ILV_ENCODE) {
+            if (!launch_encode(h, rd, rds, rp, rps, c.size, ncw, s))
+                return false;
+        } else if (c.op == ILV_DECODE) {
+            const uint8_t *pos = c.pos ? c.pos + c0 * c.pos_stride : nullptr;
+            if (!launch_decode(h, rd, rds, rp, rps, c.size, ncw, nullptr, 0, pos, nullptr, c.pos_stride,
+                               pos ? c.cnt + c0 : nullptr, c.ok + c0, c.cor ? c.cor + c0 : nullptr, s))
+                return false;
+        } else if (!launch_check(h, rd, rds, rp, rps, c.size, ncw, c.dirty + c0, s)) {
+            return false;
+        }
+        if (staged && c.op != ILV_CHECK) {
+            KernelTimer t(g, POPORON_AMD_KERNEL_ILV_SCATTER, s);
+            HIP_OK(rsk_ilv_scatter(g.ilv, fd, c.ds, fp, c.ps, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
+                                   c.op == ILV_DECODE, s));
+            t.done();
+        }
+    }
+    return !staged || rem_release(g, s);
+}
+
+static bool ilv_device(poporon_t *h, const char *what, const IlvCall &c, void *stream)
+{
+    if (!ilv_args(h, what, c))
+        return false;
+    if (c.count == 0)
+        return true;
+    if (!batch_enter(h))
+        return false;
+    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
+    DeviceGuard dg(h->gpu.device);
+    return ilv_run(h, c, (hipStream_t)stream);
+}
+
+EXPORT bool poporon_encode_interleaved_device(poporon_t *h, const uint8_t *d_data, size_t data_stride,
+                                              uint8_t *d_parity, size_t parity_stride, size_t size, size_t depth,
+                                              size_t count, void *stream)
+{
+    const IlvCall c = {ILV_ENCODE, const_cast<uint8_t *>(d_data), data_stride, d_parity, parity_stride, size, depth,
+                       count,      nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    return ilv_device(h, "poporon_encode_interleaved_device", c, stream);
+}
+
+EXPORT bool poporon_decode_interleaved_device(poporon_t *h, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                              size_t parity_stride, size_t size, size_t depth, size_t count,
+                                              const uint8_t *d_positions, size_t positions_stride,
+                                              const uint8_t *d_counts, uint8_t *d_ok, uint8_t *d_corrected,
+                                              void *stream)
+{
+    const IlvCall c = {ILV_DECODE, d_data,      data_stride,      d_parity, parity_stride, size,        depth,
+                       count,      d_positions, positions_stride, d_counts, d_ok,          d_corrected, nullptr};
+    return ilv_device(h, "poporon_decode_interleaved_device", c, stream);
+}
+
+EXPORT bool poporon_check_interleaved_device(poporon_t *h, const uint8_t *d_data, size_t data_stride,
+                                             const uint8_t *d_parity, size_t parity_stride, size_t size, size_t depth,
+                                             size_t count, uint8_t *d_dirty, void *stream)
+{
+    const IlvCall c = {ILV_CHECK, const_cast<uint8_t *>(d_data), data_stride, const_cast<uint8_t *>(d_parity),
+                       parity_stride, size, depth, count, nullptr, 0, nullptr, nullptr, nullptr, d_dirty};
+    return ilv_device(h, "poporon_check_interleaved_device", c, stream);
+}
+
+EXPORT bool poporon_amd_reserve_interleaved(poporon_t *h, size_t max_codewords)
+{
+    if (!h)
+        return fail("NULL handle");
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("poporon_amd_reserve_interleaved serves RS handles");
+    if (!gpu_init(h))
+        return false;
+    DeviceGuard dg(h->gpu.device);
+    /* a chunk is ilv_chunk codewords at most, or one frame where that is more */
+    const size_t n = std::min(max_codewords, std::max(h->ilv_chunk, (size_t)RS_ILV_MAX_DEPTH));
+    return ensure_ilv(h, n) && ensure_rem(h, n);
+}
+
+/* Host forms: chunks of frames through one pinned slot and the device form,
+ * synchronously.  Slot layout for n frames of ncw codewords, as wire blocks:
+ * [frames (size + nr) depth n | to 16 | positions nr ncw | counts ncw | ok ncw | corrected ncw] */
+static const size_t kIlvHostBytes = (size_t)8 << 20;
+
+static bool ilv_host(poporon_t *h, const char *what, const IlvCall &c)
+{
+    if (!ilv_args(h, what, c))
+        return false;
+    if (c.count == 0)
+        return true;
+    if (!batch_enter(h))
+        return false;
+    BatchScope bsc{h->gpu, nullptr, true};
+    DeviceGuard dg(h->gpu.device);
+    const size_t nr = h->rs->num_roots, db = c.size * c.depth, pb = nr * c.depth, fb = db + pb;
+    const size_t eb = c.pos ? nr : 0; /* erasure slots per codeword */
+    const size_t chunk = std::max<size_t>(1, std::min(c.count, kIlvHostBytes / (fb + c.depth * (eb + 3))));
+    auto o_pos = [&](size_t n) { return rs_ws_round16(n * fb); };
+    auto o_cnt = [&](size_t n) { return o_pos(n) + n * c.depth * eb; };
+    auto o_ok = [&](size_t n) { return o_cnt(n) + n * c.depth; };
+    auto o_cor = [&](size_t n) { return o_ok(n) + n * c.depth; };
+    GpuCtx::PipeSlot &ps = h->gpu.pipe[0];
+    if (!pipe_slot(h, ps, o_cor(chunk) + chunk * c.depth))
+        return false;
+    for (size_t f0 = 0; f0 < c.count; f0 += chunk) {
+        const size_t n = std::min(chunk, c.count - f0), ncw = n * c.depth, c0 = f0 * c.depth;
+        copy_rows(ps.host, fb, c.data + f0 * c.ds, c.ds, db, n);
+        if (c.op != ILV_ENCODE)
+            copy_rows(ps.host + db, fb, c.par + f0 * c.ps, c.ps, pb, n);
+        if (c.pos) {
+            copy_rows(ps.host + o_pos(n), nr, c.pos + c0 * c.pos_stride, c.pos_stride, nr, ncw);
+            memcpy(ps.host + o_cnt(n), c.cnt + c0, ncw);
+        }
+        const IlvCall d = {c.op,  ps.dev,
+                           fb,    ps.dev + db,
+                           fb,    c.size,
+                           c.depth, n,
+                           c.pos ? ps.dev + o_pos(n) : nullptr, nr,
+                           ps.dev + o_cnt(n), ps.dev + o_ok(n),
+                           ps.dev + o_cor(n), nullptr};
+        bool good = hipMemcpyAsync(ps.dev, ps.host, o_ok(n), hipMemcpyHostToDevice, ps.stream) == hipSuccess &&
+                    ilv_run(h, d, ps.stream) &&
+                    hipMemcpyAsync(ps.host, ps.dev, n * fb, hipMemcpyDeviceToHost, ps.stream) == hipSuccess;
+        if (good && c.op == ILV_DECODE)
+            good = hipMemcpyAsync(ps.host + o_ok(n), ps.dev + o_ok(n), 2 * ncw, hipMemcpyDeviceToHost, ps.stream) ==
+                   hipSuccess;
+        if (!good || hipStreamSynchronize(ps.stream) != hipSuccess) {
+            const std::string msg =
+                g_last_error.empty() ? std::string("HIP failure in an interleaved host batch") : g_last_error;
+            (void)hipStreamSynchronize(ps.stream);
+            return fail("%s", msg.c_str());
+        }
+        copy_rows(c.par + f0 * c.ps, c.ps, ps.host + db, fb, pb, n);
+        if (c.op == ILV_DECODE) {
+            copy_rows(c.data + f0 * c.ds, c.ds, ps.host, fb, db, n);
+            memcpy(c.ok + c0, ps.host + o_ok(n), ncw);
+            if (c.cor)
+                memcpy(c.cor + c0, ps.host + o_cor(n), ncw);
+        }
+    }
+    return true;
+}
+
+EXPORT bool poporon_encode_interleaved(poporon_t *h, const uint8_t *data, size_t data_stride, uint8_t *parity,
+                                       size_t parity_stride, size_t size, size_t depth, size_t count)
+{
+    const IlvCall c = {ILV_ENCODE, const_cast<uint8_t *>(data), data_stride, parity, parity_stride, size, depth,
+                       count,      nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    return ilv_host(h, "poporon_encode_interleaved", c);
+}
+
+EXPORT bool poporon_decode_interleaved(poporon_t *h, uint8_t *data, size_t data_stride, uint8_t *parity,
+                                       size_t parity_stride, size_t size, size_t depth, size_t count,
+                                       const uint8_t *positions, size_t positions_stride, const uint8_t *counts,
+                                       uint8_t *ok, uint8_t *corrected)
+{
+    const IlvCall c = {ILV_DECODE, data,      data_stride,      parity, parity_stride, size,      depth,
+                       count,      positions, positions_stride, counts, ok,            corrected, nullptr};
+    return ilv_host(h, "poporon_decode_interleaved", c);
 }
 
 /* ------------------------------------------------------------------------ */

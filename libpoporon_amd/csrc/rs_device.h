@@ -392,6 +392,29 @@ hipError_t rsk_forney32(const RsDevTables *tab, const RsCorrParams *prm, const R
                         size_t pos_stride, size_t count, uint8_t *ok, uint8_t *corrected, uint32_t only_pend,
                         int num_cu, hipStream_t stream);
 
+/*
+ * Symbol-interleaved frames (rs_interleave.hip): frame f holds `depth`
+ * codewords, message symbol j of codeword i at data[f*dstride + j*depth + i],
+ * parity symbol p at parity[f*pstride + p*depth + i]; row c = f*depth + i of
+ * the staging buffer is rows[c*(size + nr) ..], message then parity, the rows
+ * back to back.
+ *   rsk_ilv_gather   frames -> rows: the message region, and the parity region
+ *                    when with_parity
+ *   rsk_ilv_scatter  rows -> frames: the parity region, and the message region
+ *                    when with_data
+ * size + nr <= 255, 1 <= depth <= RS_ILV_MAX_DEPTH; regions and rows at any
+ * alignment.  Nothing outside the regions and the rows is read or written.
+ */
+#define RS_ILV_ROW 256u       /* staging bytes allocated per codeword (a row takes size + nr <= 255) */
+#define RS_ILV_LDS 32768u     /* LDS bytes of a workgroup's tile of frames */
+#define RS_ILV_MAX_DEPTH 64u
+hipError_t rsk_ilv_gather(const uint8_t *data, size_t dstride, const uint8_t *parity, size_t pstride, uint8_t *rows,
+                          uint32_t size, uint32_t nr, uint32_t depth, size_t nframes, bool with_parity,
+                          hipStream_t stream);
+hipError_t rsk_ilv_scatter(const uint8_t *rows, uint8_t *data, size_t dstride, uint8_t *parity, size_t pstride,
+                           uint32_t size, uint32_t nr, uint32_t depth, size_t nframes, bool with_data,
+                           hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

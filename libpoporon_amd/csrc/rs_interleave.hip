@@ -1,0 +1,311 @@
+/*
+ * rs_interleave.hip -- symbol-interleaved frames <-> codeword rows (gfx950).
+ *
+ * A frame of depth D holds D codewords of W = size + nr symbols: byte j*D + i
+ * of its message region is message symbol j of codeword i, byte p*D + i of its
+ * parity region parity symbol p.  The codec kernels take rows, so the
+ * interleaved entry points (api.cpp) move a chunk of frames into a staging
+ * buffer of wire rows (W bytes back to back, parity at byte `size`: the row
+ * layout the codec kernels are measured on, and the one their block apply
+ * takes), run the row kernels there and move the results back:
+ *
+ *   rs_ilv_gather_k   frames -> rows   (message only, or message and parity)
+ *   rs_ilv_scatter_k  rows -> frames   (parity only, or message and parity)
+ *
+ * Both are byte-matrix transposes [W][D] <-> [D][W] per frame.  A workgroup
+ * of 256 lanes takes a tile of whole frames whose rows fit RS_ILV_LDS bytes
+ * of LDS, so that several groups share a CU.
+ *
+ * Both sides of a tile are contiguous runs of bytes at any alignment: a
+ * frame's region, and the tile's rows in the staging buffer.  A run is cut at
+ * the 16-byte boundaries of its own address: a lane takes one 16-byte slot,
+ * as one uint4 access when the slot lies inside the run, byte by byte over
+ * the part inside it at the run's head and tail (nothing outside a run is
+ * read or written).
+ *
+ * LDS holds the image of the tile's staging rows, byte t of the run at LDS
+ * byte (run address & 15) + t, so a 16-byte slot of the run is a 16-byte
+ * aligned slot of LDS and the row side is uint4 copies (ds_read_b128 /
+ * ds_write_b128, consecutive lanes on consecutive slots).  On the frame side
+ * the 16 bytes of a slot go to / come from LDS one by one at the transposed
+ * index r*W + j.  The byte accesses bank as dword accesses do, (a / 4) mod 32
+ * within a 32-lane half, and the lanes of a half hold 32 consecutive slots,
+ * 512 bytes of a region.  For D = 4, 8 and 16 their k-th bytes are one
+ * codeword's symbols 4, 2 and 1 apart: one row, consecutive dwords (1, 2 and
+ * 4 lanes per dword).  For D = 64 they fall in four rows 16 apart, 16 W bytes:
+ * with W = 255 that is 1020 dwords, banks 0, 28, 24 and 20, two or three
+ * dwords each, so they meet on no bank; the row pitch W is the padding (an
+ * odd W never puts rows 16 apart on one bank; a shortened code whose W is a
+ * multiple of 8 does, up to 4-way at D = 64).
+ */
+#include "rs_device.h"
+
+#define RS_ILV_THREADS 256
+#define RS_ILV_BATCH 4u /* 16-byte global loads a lane keeps in flight */
+
+/* the part [kb, ke) of 16-byte slot q of a region at p (len bytes) that lies
+ * inside it; o0 = the slot's offset from p (negative in the head slot) */
+static __device__ __forceinline__ bool ilv_slot(const uint8_t *p, uint32_t len, uint32_t q, int32_t &o0, uint32_t &kb,
+                                                uint32_t &ke)
+{
+    const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u);
+    o0 = (int32_t)(q * 16u) - (int32_t)head;
+    if (o0 >= (int32_t)len)
+        return false;
+    kb = o0 < 0 ? (uint32_t)(-o0) : 0u;
+    ke = (int32_t)len - o0 < 16 ? (uint32_t)((int32_t)len - o0) : 16u;
+    return kb < ke;
+}
+
+/* 16 bytes of slot [kb, ke) at p + o0: one uint4 load when whole, else its
+ * bytes.  A wave takes the byte path whenever one of its 64 slots is a run's
+ * head or tail, which at small depths is nearly every wave, so the 16 byte
+ * loads carry no branch and do not wait for one another: byte k outside
+ * [kb, ke) re-reads the nearest byte inside it (never one outside the run)
+ * and is not used. */
+static __device__ __forceinline__ uint4 ilv_load16(const uint8_t *p, int32_t o0, uint32_t kb, uint32_t ke)
+{
+    if (kb == 0u && ke == 16u)
+        return *reinterpret_cast<const uint4 *>(p + o0);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; k++) {
+        const uint32_t kk = k < kb ? kb : k >= ke ? ke - 1u : k;
+        w[k >> 2] |= (uint32_t)p[o0 + (int32_t)kk] << (8u * (k & 3u));
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+/* frames -> LDS rows (row pitch `pitch` bytes): region of nsym symbols per
+ * codeword (nsym * depth bytes per frame, `stride` apart), LDS columns col0 ..
+ * col0 + nsym.  A lane loads RS_ILV_BATCH slots before it spreads the first:
+ * the loads' latency is paid once per batch, not once per slot. */
+static __device__ void ilv_region_in(uint8_t *lds, uint32_t pitch, const uint8_t *reg, size_t stride, uint32_t nsym,
+                                     uint32_t depth, uint32_t col0, uint32_t f0, uint32_t fc)
+{
+    const uint32_t len = nsym * depth;
+    const uint32_t nq = len / 16u + 2u; /* slots a region can touch at the worst alignment */
+    for (uint32_t base = threadIdx.x; base < fc * nq; base += RS_ILV_THREADS * RS_ILV_BATCH) {
+        uint4 v[RS_ILV_BATCH];
+        uint32_t fi[RS_ILV_BATCH], kb[RS_ILV_BATCH], ke[RS_ILV_BATCH];
+        int32_t o0[RS_ILV_BATCH];
+#pragma unroll
+        for (uint32_t u = 0; u < RS_ILV_BATCH; u++) {
+            const uint32_t idx = base + u * RS_ILV_THREADS;
+            kb[u] = ke[u] = 0u; /* nothing of this slot */
+            if (idx < fc * nq) {
+                fi[u] = idx / nq;
+                const uint8_t *p = reg + (size_t)(f0 + fi[u]) * stride;
+                if (ilv_slot(p, len, idx - fi[u] * nq, o0[u], kb[u], ke[u]))
+                    v[u] = ilv_load16(p, o0[u], kb[u], ke[u]);
+                else
+                    kb[u] = ke[u] = 0u;
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < RS_ILV_BATCH; u++) {
+            if (kb[u] >= ke[u])
+                continue;
+            const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            const uint32_t o = (uint32_t)(o0[u] + (int32_t)kb[u]);
+            uint32_t j = o / depth, i = o - j * depth;
+            const uint32_t r0 = fi[u] * depth;
+#pragma unroll
+            for (uint32_t k = 0; k < 16u; k++) {
+                if (k >= kb[u] && k < ke[u]) {
+                    lds[(r0 + i) * pitch + col0 + j] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
+                    if (++i == depth) {
+                        i = 0u;
+                        j++;
+                    }
+                }
+            }
+        }
+    }
+}
+
+/* LDS rows -> frames, the same walk */
+static __device__ void ilv_region_out(const uint8_t *lds, uint32_t pitch, uint8_t *reg, size_t stride, uint32_t nsym,
+                                      uint32_t depth, uint32_t col0, uint32_t f0, uint32_t fc)
+{
+    const uint32_t len = nsym * depth;
+    const uint32_t nq = len / 16u + 2u;
+    for (uint32_t idx = threadIdx.x; idx < fc * nq; idx += RS_ILV_THREADS) {
+        const uint32_t fi = idx / nq, q = idx - fi * nq;
+        uint8_t *p = reg + (size_t)(f0 + fi) * stride;
+        int32_t o0;
+        uint32_t kb, ke;
+        if (!ilv_slot(p, len, q, o0, kb, ke))
+            continue;
+        const uint32_t o = (uint32_t)(o0 + (int32_t)kb);
+        uint32_t j = o / depth, i = o - j * depth;
+        const uint32_t r0 = fi * depth;
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; k++) {
+            if (k >= kb && k < ke) {
+                w[k >> 2] |= (uint32_t)lds[(r0 + i) * pitch + col0 + j] << (8u * (k & 3u));
+                if (++i == depth) {
+                    i = 0u;
+                    j++;
+                }
+            }
+        }
+        if (kb == 0u && ke == 16u) {
+            *reinterpret_cast<uint4 *>(p + o0) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < 16u; k++)
+                if (k >= kb && k < ke)
+                    p[o0 + (int32_t)k] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
+        }
+    }
+}
+
+struct RsIlvArgs {
+    uint8_t *data, *parity; /* frame f's regions at data + f * dstride, parity + f * pstride */
+    size_t dstride, pstride;
+    uint8_t *rows;          /* staging: row c at rows + c * (size + nr), c = f * depth + i */
+    uint32_t size, nr, depth;
+    uint32_t nframes;       /* frames of this launch */
+    uint32_t tile;          /* frames per workgroup */
+    uint32_t both;          /* gather: the parity region too; scatter: the message region too */
+};
+
+__global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_gather_k(RsIlvArgs a)
+{
+    __shared__ uint4 lds128[RS_ILV_LDS / 16];
+    const uint32_t f0 = blockIdx.x * a.tile;
+    if (f0 >= a.nframes)
+        return;
+    const uint32_t fc = a.nframes - f0 < a.tile ? a.nframes - f0 : a.tile;
+    const uint32_t w = a.size + a.nr, len = fc * a.depth * w;
+    uint8_t *run = a.rows + (size_t)f0 * a.depth * w; /* the tile's rows */
+    const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(run) & 15u);
+    uint8_t *lds = reinterpret_cast<uint8_t *>(lds128) + head;
+    ilv_region_in(lds, w, a.data, a.dstride, a.size, a.depth, 0u, f0, fc);
+    if (a.both)
+        ilv_region_in(lds, w, a.parity, a.pstride, a.nr, a.depth, a.size, f0, fc);
+    __syncthreads();
+    /* rows out (without the parity region its columns carry whatever LDS held:
+     * they are the rows' own bytes, which the encode then writes) */
+    const uint32_t nq = (head + len + 15u) / 16u;
+    for (uint32_t q = threadIdx.x; q < nq; q += RS_ILV_THREADS) {
+        int32_t o0;
+        uint32_t kb, ke;
+        if (!ilv_slot(run, len, q, o0, kb, ke))
+            continue;
+        if (kb == 0u && ke == 16u) {
+            *reinterpret_cast<uint4 *>(run + o0) = lds128[q];
+        } else {
+            for (uint32_t k = kb; k < ke; k++)
+                run[o0 + (int32_t)k] = lds[o0 + (int32_t)k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_scatter_k(RsIlvArgs a)
+{
+    __shared__ uint4 lds128[RS_ILV_LDS / 16];
+    const uint32_t f0 = blockIdx.x * a.tile;
+    if (f0 >= a.nframes)
+        return;
+    const uint32_t fc = a.nframes - f0 < a.tile ? a.nframes - f0 : a.tile;
+    const uint32_t w = a.size + a.nr, len = fc * a.depth * w;
+    const uint8_t *run = a.rows + (size_t)f0 * a.depth * w;
+    const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(run) & 15u);
+    uint8_t *lds = reinterpret_cast<uint8_t *>(lds128) + head;
+    /* rows in, RS_ILV_BATCH loads in flight per lane; parity only: the slots
+     * that hold message bytes alone are passed by */
+    const uint32_t nq = (head + len + 15u) / 16u;
+    for (uint32_t base = threadIdx.x; base < nq; base += RS_ILV_THREADS * RS_ILV_BATCH) {
+        uint4 v[RS_ILV_BATCH];
+        uint32_t kb[RS_ILV_BATCH], ke[RS_ILV_BATCH];
+        int32_t o0[RS_ILV_BATCH];
+#pragma unroll
+        for (uint32_t u = 0; u < RS_ILV_BATCH; u++) {
+            const uint32_t q = base + u * RS_ILV_THREADS;
+            kb[u] = ke[u] = 0u;
+            if (q >= nq || !ilv_slot(run, len, q, o0[u], kb[u], ke[u])) {
+                kb[u] = ke[u] = 0u;
+                continue;
+            }
+            if (!a.both && (uint32_t)(o0[u] + (int32_t)kb[u]) % w + (ke[u] - kb[u]) <= a.size) {
+                kb[u] = ke[u] = 0u;
+                continue;
+            }
+            v[u] = ilv_load16(run, o0[u], kb[u], ke[u]);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < RS_ILV_BATCH; u++) {
+            if (kb[u] >= ke[u])
+                continue;
+            if (kb[u] == 0u && ke[u] == 16u) {
+                lds128[base + u * RS_ILV_THREADS] = v[u];
+            } else {
+                const uint32_t x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+                for (uint32_t k = 0; k < 16u; k++)
+                    if (k >= kb[u] && k < ke[u])
+                        lds[o0[u] + (int32_t)k] = (uint8_t)(x[k >> 2] >> (8u * (k & 3u)));
+            }
+        }
+    }
+    __syncthreads();
+    if (a.both)
+        ilv_region_out(lds, w, a.data, a.dstride, a.size, a.depth, 0u, f0, fc);
+    ilv_region_out(lds, w, a.parity, a.pstride, a.nr, a.depth, a.size, f0, fc);
+}
+
+/* whole frames per workgroup for a code of w = size + nr symbols at `depth`:
+ * their rows, and up to 15 bytes of alignment before them, in RS_ILV_LDS bytes
+ * (one frame of 64 rows of 255 symbols: 16,320 B) */
+static bool ilv_tile(uint32_t w, uint32_t depth, uint32_t &tile)
+{
+    if (w == 0u || w > RS_ILV_ROW - 1u || depth == 0u || depth > RS_ILV_MAX_DEPTH)
+        return false;
+    tile = (RS_ILV_LDS - 16u) / (w * depth);
+    return tile >= 1u;
+}
+
+static hipError_t ilv_launch(bool gather, uint8_t *data, size_t dstride, uint8_t *parity, size_t pstride, uint8_t *rows,
+                             uint32_t size, uint32_t nr, uint32_t depth, size_t nframes, bool both, hipStream_t stream)
+{
+    RsIlvArgs a;
+    a.data = data;
+    a.parity = parity;
+    a.dstride = dstride;
+    a.pstride = pstride;
+    a.rows = rows;
+    a.size = size;
+    a.nr = nr;
+    a.depth = depth;
+    a.both = both ? 1u : 0u;
+    if (!ilv_tile(size + nr, depth, a.tile) || nframes > 0x7FFFFFFFu / RS_ILV_MAX_DEPTH)
+        return hipErrorInvalidValue;
+    if (nframes == 0)
+        return hipSuccess;
+    a.nframes = (uint32_t)nframes;
+    const uint32_t grid = (a.nframes + a.tile - 1u) / a.tile;
+    if (gather)
+        RS_LAUNCH(rs_ilv_gather_k, dim3(grid), dim3(RS_ILV_THREADS), 0, stream, a);
+    else
+        RS_LAUNCH(rs_ilv_scatter_k, dim3(grid), dim3(RS_ILV_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rsk_ilv_gather(const uint8_t *data, size_t dstride, const uint8_t *parity, size_t pstride,
+                                     uint8_t *rows, uint32_t size, uint32_t nr, uint32_t depth, size_t nframes,
+                                     bool with_parity, hipStream_t stream)
+{
+    return ilv_launch(true, const_cast<uint8_t *>(data), dstride, const_cast<uint8_t *>(parity), pstride, rows, size,
+                      nr, depth, nframes, with_parity, stream);
+}
+
+extern "C" hipError_t rsk_ilv_scatter(const uint8_t *rows, uint8_t *data, size_t dstride, uint8_t *parity,
+                                      size_t pstride, uint32_t size, uint32_t nr, uint32_t depth, size_t nframes,
+                                      bool with_data, hipStream_t stream)
+{
+    return ilv_launch(false, data, dstride, parity, pstride, const_cast<uint8_t *>(rows), size, nr, depth, nframes,
+                      with_data, stream);
+}
