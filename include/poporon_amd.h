@@ -181,6 +181,91 @@ bool poporon_decode_interleaved(poporon_t *pprn, uint8_t *data, size_t data_stri
                                 uint8_t *corrected);
 bool poporon_amd_reserve_interleaved(poporon_t *pprn, size_t max_codewords);
 
+/* ---- decode reports: where the errors were -----------------------------------
+ * poporon_decode_batch_report_device takes poporon_decode_batch_device's
+ * arguments and three more arrays, poporon_decode_interleaved_report_device
+ * poporon_decode_interleaved_device's and the same three.  RS handles only
+ * (BCH and LDPC handles: false with a message).  The contract:
+ *
+ *  - Data, parity, d_ok and d_corrected come out exactly as from
+ *    poporon_decode_batch_device (poporon_decode_interleaved_device) with the
+ *    same arguments; erasure lists are passed through unchanged.
+ *  - The report lists the bytes of codeword c that the call changed, ascending
+ *    by position; d_err_num[c] is how many.  For k < d_err_num[c],
+ *    d_err_pos[c*report_stride + k] is the position: 0 .. size-1 is message
+ *    symbol pos, size .. size+num_roots-1 parity symbol pos - size (positions
+ *    fit a byte: size + num_roots <= 255), and d_err_val[c*report_stride + k]
+ *    is before XOR after, so XORing the report into the returned row gives the
+ *    received row back.  A list is capped at num_roots entries; the reference
+ *    never applies more corrections than that.
+ *  - Slots d_err_num[c] .. num_roots-1 of both arrays are written 0; bytes
+ *    num_roots .. report_stride are never written.  report_stride >=
+ *    num_roots, or the call fails.
+ *  - Interleaved form: c = f*depth + i, and positions are symbol indices
+ *    within the codeword, not byte offsets in the frame.
+ *  - The report is NOT corrected_num in another form.  d_corrected[c] counts
+ *    the non-zero magnitudes the decoder computed, whether or not they were
+ *    applied: a codeword that fails late (d_ok[c] = 0) can have d_corrected[c]
+ *    > 0 and come back unchanged, and its report is empty (d_err_num[c] = 0).
+ *    On successful rows the two usually agree; duplicate or stale erasure
+ *    slots (quirks Q1/Q2) and an erased symbol whose value was right can make
+ *    them differ.  The report defines nothing beyond the diff of the rows.
+ *
+ * How: per chunk the rows are copied to a snapshot buffer the handle owns
+ * (wire rows, 256 B per codeword allocated: one device copy when the caller's
+ * rows are wire rows already, d_parity = d_data + size and both strides size +
+ * num_roots, else a gather kernel), the decode runs in place as the plain
+ * call's does, and a kernel lists where the rows differ from the snapshot; the
+ * interleaved form snapshots its staging rows after the gather.  A chunk is at
+ * most 2^20 codewords (POPORON_AMD_REPORT_CHUNK=<codewords> in the environment
+ * at poporon_create; the interleaved form at depth > 1 goes by
+ * POPORON_AMD_ILV_CHUNK); larger batches run chunk after chunk on `stream`,
+ * each routed by its own count.  poporon_amd_reserve_report sizes the snapshot
+ * buffer for min(max_codewords, chunk) codewords and does for that count what
+ * poporon_amd_reserve does, so that later row report calls allocate nothing
+ * (the interleaved form also needs poporon_amd_reserve_interleaved).  The rows
+ * take the report kernel's fast path when they are wire rows on a 16-byte
+ * aligned base.  The host form moves chunks of rows through pinned memory of
+ * its own and returns when the results are in host memory. */
+bool poporon_decode_batch_report_device(poporon_t *pprn, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                        size_t parity_stride, size_t size, size_t count, const uint8_t *d_positions,
+                                        size_t positions_stride, const uint8_t *d_counts, uint8_t *d_ok,
+                                        uint8_t *d_corrected, uint8_t *d_err_num, uint8_t *d_err_pos,
+                                        uint8_t *d_err_val, size_t report_stride, void *stream);
+bool poporon_decode_interleaved_report_device(poporon_t *pprn, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                              size_t parity_stride, size_t size, size_t depth, size_t count,
+                                              const uint8_t *d_positions, size_t positions_stride,
+                                              const uint8_t *d_counts, uint8_t *d_ok, uint8_t *d_corrected,
+                                              uint8_t *d_err_num, uint8_t *d_err_pos, uint8_t *d_err_val,
+                                              size_t report_stride, void *stream);
+bool poporon_decode_batch_report(poporon_t *pprn, uint8_t *data, size_t data_stride, uint8_t *parity,
+                                 size_t parity_stride, size_t size, size_t count, const uint8_t *positions,
+                                 size_t positions_stride, const uint8_t *counts, uint8_t *ok, uint8_t *corrected,
+                                 uint8_t *err_num, uint8_t *err_pos, uint8_t *err_val, size_t report_stride);
+bool poporon_amd_reserve_report(poporon_t *pprn, size_t max_codewords);
+
+/* ---- erasure lists from a flag plane ------------------------------------------
+ * d_mask has the layout of the message regions: frame f has size*depth bytes
+ * at d_mask + f*mask_stride, the flag of symbol j of codeword i at j*depth + i
+ * (depth 1: rows); a non-zero byte means erased.  For codeword c = f*depth + i
+ * the first num_roots flagged symbol indices are written ascending to
+ * d_positions[c*positions_stride ..], the slots behind them up to num_roots 0
+ * (the decoders read those slots, quirks Q2/Q3), bytes num_roots ..
+ * positions_stride never; d_counts[c] = min(flagged, num_roots); d_over[c]
+ * (may be NULL) = 1 when more than num_roots symbols were flagged: such a
+ * codeword is beyond an erasure decode, and the caller decides what to do with
+ * it.  Ascending lists are what the decoders need (quirk Q1: magnitudes pair
+ * with list slots in ascending location order).  positions_stride >=
+ * num_roots, mask_stride >= size*depth, 1 <= depth <= 64, count frames, RS
+ * handles only.  The outputs feed poporon_decode_batch_device /
+ * poporon_decode_interleaved_device (and their report forms) directly; a
+ * positions_stride of 32 on a 16-byte aligned base keeps the 32-erasure
+ * kernel's fast route.  There is no host form: on the host np.nonzero or a
+ * loop does this. */
+bool poporon_amd_erasures_from_mask_device(poporon_t *pprn, const uint8_t *d_mask, size_t mask_stride, size_t size,
+                                           size_t depth, size_t count, uint8_t *d_positions, size_t positions_stride,
+                                           uint8_t *d_counts, uint8_t *d_over, void *stream);
+
 /* ---- LDPC batches -----------------------------------------------------------
  * Row c has info_bytes (poporon_get_info_size) of data at d_data +
  * c*data_stride and parity_bytes (poporon_get_parity_size) of parity at
@@ -265,6 +350,10 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
  * (rs_ilv_gather_k), 16 = rows back to frames (rs_ilv_scatter_k), one launch
  * each per chunk; the codec kernels between them keep their ids, routed by the
  * chunk's codeword count.
+ * The report calls: 17 = the snapshot of a chunk's rows (a device copy, or
+ * rs_snapshot_k for rows that are not wire rows), 18 = rs_report_k, one each
+ * per chunk, around the decode's own ids.  19 = rs_mask_lists_k
+ * (poporon_amd_erasures_from_mask_device).
  *
  * Error- and erasure-mode batches of at least 16384 codewords take the split
  * decode; POPORON_AMD_DECODE_PATH=split / single / wave in the environment
@@ -287,6 +376,9 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
 #define POPORON_AMD_KERNEL_LDPC_CHECK 14
 #define POPORON_AMD_KERNEL_ILV_GATHER 15
 #define POPORON_AMD_KERNEL_ILV_SCATTER 16
+#define POPORON_AMD_KERNEL_SNAPSHOT 17
+#define POPORON_AMD_KERNEL_REPORT 18
+#define POPORON_AMD_KERNEL_MASK_LISTS 19
 bool poporon_amd_timing(poporon_t *pprn, int enable);
 bool poporon_amd_timing_read(poporon_t *pprn, int kernel, double *total_ms, uint64_t *launches);
 

@@ -97,6 +97,17 @@ _SIGS = {
     "poporon_decode_interleaved": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                               C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp]),
     "poporon_amd_reserve_interleaved": (C.c_bool, [_vp, C.c_size_t]),
+    "poporon_decode_batch_report_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                      _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                                      _vp]),
+    "poporon_decode_interleaved_report_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t,
+                                                            C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp,
+                                                            _vp, _vp, _vp, C.c_size_t, _vp]),
+    "poporon_decode_batch_report": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp,
+                                               C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
+    "poporon_amd_reserve_report": (C.c_bool, [_vp, C.c_size_t]),
+    "poporon_amd_erasures_from_mask_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                         _vp, C.c_size_t, _vp, _vp, _vp]),
     "poporon_rng_create": (_vp, [C.c_int, _vp, C.c_size_t]),
     "poporon_rng_destroy": (None, [_vp]),
     "poporon_rng_next": (C.c_bool, [_vp, _vp, C.c_size_t]),
@@ -134,6 +145,7 @@ KERNEL_BM, KERNEL_CHIEN, KERNEL_FORNEY, KERNEL_LIST, KERNEL_APPLY, KERNEL_ERASUR
 KERNEL_WAVE = 11
 KERNEL_LDPC_ENCODE, KERNEL_LDPC_DECODE, KERNEL_LDPC_CHECK = 12, 13, 14
 KERNEL_ILV_GATHER, KERNEL_ILV_SCATTER = 15, 16
+KERNEL_SNAPSHOT, KERNEL_REPORT, KERNEL_MASK_LISTS = 17, 18, 19
 KERNEL_NAMES = {KERNEL_ENCODE: "rs_lfsr_k<false> (encode)", KERNEL_REMAINDER: "rs_lfsr_k<true> (remainder)",
                 KERNEL_CORRECT: "rs_correct_k (BM/Chien/Forney)", KERNEL_BM: "rs_bm_k (BM/Omega)",
                 KERNEL_CHIEN: "rs_chien_k (Chien)", KERNEL_FORNEY: "rs_forney_k (Forney)",
@@ -142,6 +154,8 @@ KERNEL_NAMES = {KERNEL_ENCODE: "rs_lfsr_k<false> (encode)", KERNEL_REMAINDER: "r
                 KERNEL_WAVE: "rs_wave_k (small batch)"}
 ILV_KERNEL_NAMES = {KERNEL_ILV_GATHER: "rs_ilv_gather_k (frames to rows)",
                     KERNEL_ILV_SCATTER: "rs_ilv_scatter_k (rows to frames)"}
+REPORT_KERNEL_NAMES = {KERNEL_SNAPSHOT: "snapshot (device copy or rs_snapshot_k)", KERNEL_REPORT: "rs_report_k",
+                       KERNEL_MASK_LISTS: "rs_mask_lists_k"}
 LDPC_KERNEL_NAMES = {KERNEL_LDPC_ENCODE: "ldpc_encode_k", KERNEL_LDPC_DECODE: "ldpc_decode_k",
                      KERNEL_LDPC_CHECK: "ldpc_check_k"}
 
@@ -441,6 +455,59 @@ class Poporon:
                                                         depth, count, *pargs, _buf(ok), _buf(cor)),
                     "poporon_decode_interleaved")
         return ok, cor, d, p
+
+    # ---- decode reports and erasure lists from flag planes (include/poporon_amd.h) ---
+    # the report of codeword c: d_err_num[c] changed bytes, their positions (0 .. size-1 message,
+    # size .. parity) and before ^ after at d_err_pos / d_err_val + c*report_stride
+    def decode_batch_report_device(self, d_data, data_stride, d_parity, parity_stride, size, count, d_ok,
+                                   d_err_num, d_err_pos, d_err_val, report_stride, d_corrected=None,
+                                   d_positions=None, positions_stride=0, d_counts=None, stream=0):
+        self._check(self.lib.poporon_decode_batch_report_device(self.h, d_data, data_stride, d_parity, parity_stride,
+                                                                size, count, d_positions, positions_stride, d_counts,
+                                                                d_ok, d_corrected, d_err_num, d_err_pos, d_err_val,
+                                                                report_stride, stream or None),
+                    "poporon_decode_batch_report_device")
+
+    def decode_interleaved_report_device(self, d_data, data_stride, d_parity, parity_stride, size, depth, count, d_ok,
+                                         d_err_num, d_err_pos, d_err_val, report_stride, d_corrected=None,
+                                         d_positions=None, positions_stride=0, d_counts=None, stream=0):
+        self._check(self.lib.poporon_decode_interleaved_report_device(self.h, d_data, data_stride, d_parity,
+                                                                      parity_stride, size, depth, count, d_positions,
+                                                                      positions_stride, d_counts, d_ok, d_corrected,
+                                                                      d_err_num, d_err_pos, d_err_val, report_stride,
+                                                                      stream or None),
+                    "poporon_decode_interleaved_report_device")
+
+    def decode_batch_report(self, data, parity, positions=None, counts=None):
+        """Returns (data', parity', ok u8[count], corrected u8[count], err_num u8[count],
+        err_pos u8[count, num_roots], err_val u8[count, num_roots])."""
+        d = np.array(data, dtype=np.uint8, copy=True, order="C")
+        p = np.array(parity, dtype=np.uint8, copy=True, order="C")
+        count, size = d.shape
+        nr = self.num_roots
+        ok, cor, num = (np.zeros(count, np.uint8) for _ in range(3))
+        epos, eval_ = np.zeros((count, nr), np.uint8), np.zeros((count, nr), np.uint8)
+        if positions is not None:
+            pos = np.ascontiguousarray(positions, dtype=np.uint8)
+            cnt = np.ascontiguousarray(counts, dtype=np.uint8)
+            pargs = (_buf(pos), pos.shape[1], _buf(cnt))
+        else:
+            pargs = (None, 0, None)
+        self._check(self.lib.poporon_decode_batch_report(self.h, _buf(d), size, _buf(p), p.shape[1], size, count,
+                                                         *pargs, _buf(ok), _buf(cor), _buf(num), _buf(epos),
+                                                         _buf(eval_), nr), "poporon_decode_batch_report")
+        return d, p, ok, cor, num, epos, eval_
+
+    def reserve_report(self, max_codewords):
+        self._check(self.lib.poporon_amd_reserve_report(self.h, max_codewords), "poporon_amd_reserve_report")
+
+    def erasures_from_mask_device(self, d_mask, mask_stride, size, depth, count, d_positions, positions_stride,
+                                  d_counts, d_over=None, stream=0):
+        """flag plane in the layout of the message regions (count frames) -> ascending erasure lists"""
+        self._check(self.lib.poporon_amd_erasures_from_mask_device(self.h, d_mask, mask_stride, size, depth, count,
+                                                                   d_positions, positions_stride, d_counts, d_over,
+                                                                   stream or None),
+                    "poporon_amd_erasures_from_mask_device")
 
     # ---- in-library kernel timing (HIP events on the launch stream) ---------------
     def timing(self, enable: bool):

@@ -118,7 +118,7 @@ struct _poporon_config_t {
     uint64_t seed;
 };
 
-#define NKERN 17
+#define NKERN 20
 struct TimedLaunch {
     int kernel;
     hipEvent_t a, b;
@@ -145,6 +145,10 @@ struct GpuCtx {
      * bytes per codeword; shared across streams under rem's ordering */
     uint8_t *ilv = nullptr;
     size_t ilv_cap = 0;
+    /* the rows before a decode, for the report calls (rs_report.hip): wire rows,
+     * RS_ILV_ROW bytes per codeword allocated; ordered as ilv is */
+    uint8_t *rep = nullptr;
+    size_t rep_cap = 0;
     /* Ordering of the workspace across streams: rem_done is recorded on the
      * stream of the last launch that read rem (rem_stream); a call on another
      * stream waits for it before overwriting rem. */
@@ -185,12 +189,16 @@ struct GpuCtx {
         bool busy = false;
         size_t c0 = 0, n = 0; /* the chunk whose results the slot holds */
     } pipe[3];
+    PipeSlot rslot; /* poporon_decode_batch_report's own slot */
 };
 #define PIPE_SLOTS 3
 
 /* interleaved calls: codewords staged at a time (256 B each), default and the cap of the override */
 #define ILV_CHUNK_DEFAULT ((size_t)1 << 20)
 #define ILV_CHUNK_MAX (1ull << 24)
+/* report calls: codewords snapshotted at a time (256 B each) */
+#define REP_CHUNK_DEFAULT ((size_t)1 << 20)
+#define REP_CHUNK_MAX (1ull << 24)
 
 struct _poporon_t {
     poporon_fec_type_t fec_type;
@@ -210,6 +218,7 @@ struct _poporon_t {
     bool lfsr_nr;   /* generic code, num_roots <= 32: batch encodes on the LFSR kernel (rsk_encode_nr) */
     bool nrsplit;   /* ... and large error-mode batches decode on the split kernels (params_nrsplit) */
     size_t ilv_chunk; /* codewords the interleaved calls stage at a time (POPORON_AMD_ILV_CHUNK) */
+    size_t rep_chunk; /* codewords the report calls snapshot at a time (POPORON_AMD_REPORT_CHUNK) */
     int gen_path;   /* general kernels: 0 by batch size, 1 one codeword per lane (rsg_*), 2 one per wave
                        (rsgw_*); POPORON_AMD_GENERIC=lane|wave */
     RsDevTables host_tab;
@@ -947,6 +956,11 @@ EXPORT poporon_t *poporon_create(const poporon_config_t *config)
         const unsigned long long v = ic ? strtoull(ic, nullptr, 10) : 0ull;
         h->ilv_chunk = v ? (size_t)std::min<unsigned long long>(v, ILV_CHUNK_MAX) : ILV_CHUNK_DEFAULT;
     }
+    {
+        const char *rc = getenv("POPORON_AMD_REPORT_CHUNK");
+        const unsigned long long v = rc ? strtoull(rc, nullptr, 10) : 0ull;
+        h->rep_chunk = v ? (size_t)std::min<unsigned long long>(v, REP_CHUNK_MAX) : REP_CHUNK_DEFAULT;
+    }
     if (h->fast)
         build_tables(h);
     if (h->generic)
@@ -1079,7 +1093,7 @@ static void gpu_release(GpuCtx &g)
 {
     const int dev = g.device;
     const bool any = g.ready || g.stream || g.sstream || g.tab || g.gtab || g.rem || g.ltab || g.lws || g.stage ||
-                     g.hstage || g.zc || g.ilv ||
+                     g.hstage || g.zc || g.ilv || g.rep || g.rslot.stream ||
                      g.rem_done || g.registered || g.batch_ev ||
                      g.pipe[0].stream || g.pipe[1].stream || g.pipe[2].stream;
     if (!any || dev < 0) {
@@ -1109,6 +1123,7 @@ static void gpu_release(GpuCtx &g)
     (void)hipFree(g.gtab);
     (void)hipFree(g.rem);
     (void)hipFree(g.ilv);
+    (void)hipFree(g.rep);
     (void)hipFree(g.ltab);
     (void)hipFree(g.lws);
     (void)hipFree(g.stage);
@@ -1124,7 +1139,8 @@ static void gpu_release(GpuCtx &g)
     }
     if (g.zc)
         (void)hipHostFree(g.zc);
-    for (auto &ps : g.pipe) {
+    for (GpuCtx::PipeSlot *slot : {&g.pipe[0], &g.pipe[1], &g.pipe[2], &g.rslot}) {
+        GpuCtx::PipeSlot &ps = *slot;
         if (ps.stream)
             (void)hipStreamSynchronize(ps.stream);
         (void)hipHostFree(ps.host);
@@ -2656,6 +2672,73 @@ static bool ensure_ilv(poporon_t *h, size_t codewords)
     return true;
 }
 
+/* The report calls' snapshot buffer (rs_report.hip): the rows of a chunk as
+ * they were before the decode, wire rows in RS_ILV_ROW bytes per codeword,
+ * the handle's, grown on demand and ordered across streams as ilv is.  At
+ * least 64 codewords, so that the 16-byte slot at the end of the rows lies
+ * inside it. */
+static bool ensure_rep(poporon_t *h, size_t codewords)
+{
+    GpuCtx &g = h->gpu;
+    if (g.rep_cap >= codewords)
+        return true;
+    const size_t cap = std::max(codewords, (size_t)RS_ILV_MAX_DEPTH);
+    if (g.rep) {
+        if (g.rem_pending)
+            HIP_OK(hipEventSynchronize(g.rem_done));
+        g.rem_pending = false;
+        HIP_OK(hipFree(g.rep));
+        g.rep = nullptr;
+        g.rep_cap = 0;
+    }
+    HIP_OK(hipMalloc((void **)&g.rep, cap * RS_ILV_ROW));
+    g.rep_cap = cap;
+    return true;
+}
+
+/* where a report goes: num[c], pos / val[c * stride .. + num_roots) */
+struct RepOut {
+    uint8_t *num, *pos, *val;
+    size_t stride;
+};
+
+/* n rows -> the snapshot buffer.  Rows that are wire rows already (parity
+ * behind the message, both strides size + nr) are one device copy, stamped
+ * with the timer's events by hand since no kernel of ours runs; any other
+ * placement is gathered by rs_snapshot_k. */
+static bool rep_snapshot(poporon_t *h, const uint8_t *d, size_t ds, const uint8_t *p, size_t ps, size_t size, size_t n,
+                         hipStream_t s)
+{
+    GpuCtx &g = h->gpu;
+    const uint32_t nr = h->rs->num_roots;
+    const size_t w = size + nr;
+    KernelTimer t(g, POPORON_AMD_KERNEL_SNAPSHOT, s);
+    if (p == d + size && ds == w && ps == w) {
+        if (t.a)
+            HIP_OK(hipEventRecord(t.a, s));
+        HIP_OK(hipMemcpyAsync(g.rep, d, n * w, hipMemcpyDeviceToDevice, s));
+        if (t.a) {
+            HIP_OK(hipEventRecord(t.b, s));
+            rs_launch_timer.n = 1;
+        }
+    } else {
+        HIP_OK(rsk_snapshot(d, ds, p, ps, g.rep, (uint32_t)size, nr, n, s));
+    }
+    t.done();
+    return true;
+}
+
+/* the n rows as they are now against the snapshot buffer */
+static bool rep_diff(poporon_t *h, const uint8_t *d, size_t ds, const uint8_t *p, size_t ps, size_t size, size_t n,
+                     const RepOut &o, size_t c0, hipStream_t s)
+{
+    KernelTimer t(h->gpu, POPORON_AMD_KERNEL_REPORT, s);
+    HIP_OK(rsk_report(d, ds, p, ps, h->gpu.rep, (uint32_t)size, h->rs->num_roots, n, o.num + c0,
+                      o.pos + c0 * o.stride, o.val + c0 * o.stride, o.stride, s));
+    t.done();
+    return true;
+}
+
 enum { ILV_ENCODE, ILV_DECODE, ILV_CHECK };
 
 struct IlvCall {
@@ -2669,6 +2752,7 @@ struct IlvCall {
     size_t pos_stride;
     const uint8_t *cnt;
     uint8_t *ok, *cor, *dirty;
+    RepOut rep; /* ILV_DECODE: the report arrays (num NULL: none) */
 };
 
 static size_t ilv_chunk_frames(const poporon_t *h, size_t depth) { return std::max<size_t>(1, h->ilv_chunk / depth); }
@@ -2696,6 +2780,10 @@ static bool ilv_args(const poporon_t *h, const char *what, const IlvCall &c)
     return true;
 }
 
+static bool rep_run(poporon_t *h, uint8_t *d, size_t ds, uint8_t *p, size_t ps, size_t size, size_t count,
+                    const uint8_t *pos, size_t pos_stride, const uint8_t *cnt, uint8_t *ok, uint8_t *cor,
+                    const RepOut &o, hipStream_t s);
+
 /* device pointers; the caller holds the batch scope and the device */
 static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
 {
@@ -2703,6 +2791,12 @@ static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
     const uint32_t nr = h->rs->num_roots;
     const size_t cf = ilv_chunk_frames(h, c.depth);
     const bool staged = c.depth > 1;
+    const bool report = c.op == ILV_DECODE && c.rep.num;
+    if (report && !staged) /* depth 1 is the row layout: the row report */
+        return rep_run(h, c.data, c.ds, c.par, c.ps, c.size, c.count, c.pos, c.pos_stride, c.cnt, c.ok, c.cor, c.rep,
+                       s);
+    if (report && !ensure_rep(h, std::min(c.count, cf) * c.depth))
+        return false;
     if (staged && (!ensure_ilv(h, std::min(c.count, cf) * c.depth) || !rem_acquire(g, s)))
         return false;
     for (size_t f0 = 0; f0 < c.count; f0 += cf) {
@@ -2721,8 +2815,13 @@ static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
                 return false;
         } else if (c.op == ILV_DECODE) {
             const uint8_t *pos = c.pos ? c.pos + c0 * c.pos_stride : nullptr;
+            /* report: the staging rows as gathered are the snapshot (wire rows: one device copy) */
+            if (report && !rep_snapshot(h, rd, rds, rp, rps, c.size, ncw, s))
+                return false;
             if (!launch_decode(h, rd, rds, rp, rps, c.size, ncw, nullptr, 0, pos, nullptr, c.pos_stride,
                                pos ? c.cnt + c0 : nullptr, c.ok + c0, c.cor ? c.cor + c0 : nullptr, s))
+                return false;
+            if (report && !rep_diff(h, rd, rds, rp, rps, c.size, ncw, c.rep, c0, s))
                 return false;
         } else if (!launch_check(h, rd, rds, rp, rps, c.size, ncw, c.dirty + c0, s)) {
             return false;
@@ -2873,6 +2972,229 @@ EXPORT bool poporon_decode_interleaved(poporon_t *h, uint8_t *data, size_t data_
     const IlvCall c = {ILV_DECODE, data,      data_stride,      parity, parity_stride, size,      depth,
                        count,      positions, positions_stride, counts, ok,            corrected, nullptr};
     return ilv_host(h, "poporon_decode_interleaved", c);
+}
+
+/* ------------------------------------------------------------------------ */
+/* decode reports and erasure lists from flag planes (rs_report.hip)        */
+/* ------------------------------------------------------------------------ */
+
+/*
+ * A report is "the bytes this call changed" (poporon_amd.h): per chunk of at
+ * most rep_chunk codewords the rows are copied to the snapshot buffer, the
+ * decode runs in place through launch_decode exactly as the plain call's does
+ * (routed by the chunk's count), and rs_report_k lists where the rows now
+ * differ from the snapshot.  No codec kernel knows about it, so it is the same
+ * for every decode route.  Device pointers; the caller holds the batch scope
+ * and the device.
+ */
+static bool rep_run(poporon_t *h, uint8_t *d, size_t ds, uint8_t *p, size_t ps, size_t size, size_t count,
+                    const uint8_t *pos, size_t pos_stride, const uint8_t *cnt, uint8_t *ok, uint8_t *cor,
+                    const RepOut &o, hipStream_t s)
+{
+    GpuCtx &g = h->gpu;
+    const size_t chunk = h->rep_chunk;
+    if (!ensure_rep(h, std::min(count, chunk)) || !rem_acquire(g, s))
+        return false;
+    for (size_t c0 = 0; c0 < count; c0 += chunk) {
+        const size_t n = std::min(chunk, count - c0);
+        uint8_t *cd = d + c0 * ds, *cp = p + c0 * ps;
+        if (!rep_snapshot(h, cd, ds, cp, ps, size, n, s))
+            return false;
+        if (!launch_decode(h, cd, ds, cp, ps, size, n, nullptr, 0, pos ? pos + c0 * pos_stride : nullptr, nullptr,
+                           pos_stride, pos ? cnt + c0 : nullptr, ok + c0, cor ? cor + c0 : nullptr, s))
+            return false;
+        if (!rep_diff(h, cd, ds, cp, ps, size, n, o, c0, s))
+            return false;
+    }
+    return rem_release(g, s);
+}
+
+/* what every report entry point checks about the report arrays */
+static bool rep_args(const poporon_t *h, const char *what, size_t count, const RepOut &o)
+{
+    if (count && (!o.num || !o.pos || !o.val))
+        return fail("%s: NULL report array", what);
+    if (o.stride < h->rs->num_roots)
+        return fail("%s: report_stride %zu < num_roots (%u)", what, o.stride, (unsigned)h->rs->num_roots);
+    return true;
+}
+
+/* the row calls' own checks (poporon_decode_batch_device's, RS handles only) */
+static bool rep_row_args(const poporon_t *h, const char *what, const uint8_t *data, const uint8_t *parity, size_t size,
+                         size_t count, const uint8_t *positions, size_t positions_stride, const uint8_t *counts,
+                         const uint8_t *ok, const RepOut &o)
+{
+    if (!h)
+        return fail("%s: NULL handle", what);
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("%s serves RS handles", what);
+    if (count && (!data || !parity || !ok))
+        return fail("%s: NULL argument", what);
+    if (positions && (!counts || positions_stride < h->rs->num_roots))
+        return fail("%s: erasure batch needs counts and positions_stride >= num_roots", what);
+    if (!check_decode_size(h, size))
+        return fail("%s: size %zu outside [1, %u]", what, size, (unsigned)kmax(h));
+    return rep_args(h, what, count, o);
+}
+
+EXPORT bool poporon_decode_batch_report_device(poporon_t *h, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                               size_t parity_stride, size_t size, size_t count,
+                                               const uint8_t *d_positions, size_t positions_stride,
+                                               const uint8_t *d_counts, uint8_t *d_ok, uint8_t *d_corrected,
+                                               uint8_t *d_err_num, uint8_t *d_err_pos, uint8_t *d_err_val,
+                                               size_t report_stride, void *stream)
+{
+    const char *what = "poporon_decode_batch_report_device";
+    const RepOut o = {d_err_num, d_err_pos, d_err_val, report_stride};
+    if (!rep_row_args(h, what, d_data, d_parity, size, count, d_positions, positions_stride, d_counts, d_ok, o))
+        return false;
+    if (count == 0)
+        return true;
+    if (!batch_enter(h))
+        return false;
+    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
+    DeviceGuard dg(h->gpu.device);
+    return rep_run(h, d_data, data_stride, d_parity, parity_stride, size, count, d_positions, positions_stride,
+                   d_counts, d_ok, d_corrected, o, (hipStream_t)stream);
+}
+
+EXPORT bool poporon_decode_interleaved_report_device(poporon_t *h, uint8_t *d_data, size_t data_stride,
+                                                     uint8_t *d_parity, size_t parity_stride, size_t size,
+                                                     size_t depth, size_t count, const uint8_t *d_positions,
+                                                     size_t positions_stride, const uint8_t *d_counts, uint8_t *d_ok,
+                                                     uint8_t *d_corrected, uint8_t *d_err_num, uint8_t *d_err_pos,
+                                                     uint8_t *d_err_val, size_t report_stride, void *stream)
+{
+    const char *what = "poporon_decode_interleaved_report_device";
+    const IlvCall c = {ILV_DECODE,  d_data,           data_stride, d_parity, parity_stride, size,
+                       depth,       count,            d_positions, positions_stride,        d_counts,
+                       d_ok,        d_corrected,      nullptr,     {d_err_num, d_err_pos, d_err_val, report_stride}};
+    if (!ilv_args(h, what, c) || !rep_args(h, what, count, c.rep))
+        return false;
+    return ilv_device(h, what, c, stream);
+}
+
+EXPORT bool poporon_amd_reserve_report(poporon_t *h, size_t max_codewords)
+{
+    if (!h)
+        return fail("NULL handle");
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("poporon_amd_reserve_report serves RS handles");
+    if (!gpu_init(h))
+        return false;
+    DeviceGuard dg(h->gpu.device);
+    const size_t n = std::min(max_codewords, h->rep_chunk);
+    return ensure_rep(h, n) && ensure_rem(h, n);
+}
+
+/* Host form: chunks of rows through one pinned slot of its own and the device
+ * form, synchronously (poporon_decode_batch's pipeline is not involved).  Slot
+ * layout for n codewords:
+ * [wire rows (size + nr) n | to 16 | positions nr n | counts n | ok n | corrected n | err_num n | to 16 |
+ *  err_pos nr n | err_val nr n] */
+static const size_t kRepHostBytes = (size_t)8 << 20;
+
+EXPORT bool poporon_decode_batch_report(poporon_t *h, uint8_t *data, size_t data_stride, uint8_t *parity,
+                                        size_t parity_stride, size_t size, size_t count, const uint8_t *positions,
+                                        size_t positions_stride, const uint8_t *counts, uint8_t *ok,
+                                        uint8_t *corrected, uint8_t *err_num, uint8_t *err_pos, uint8_t *err_val,
+                                        size_t report_stride)
+{
+    const char *what = "poporon_decode_batch_report";
+    const RepOut o = {err_num, err_pos, err_val, report_stride};
+    if (!rep_row_args(h, what, data, parity, size, count, positions, positions_stride, counts, ok, o))
+        return false;
+    if (count == 0)
+        return true;
+    if (!batch_enter(h))
+        return false;
+    BatchScope bsc{h->gpu, nullptr, true};
+    DeviceGuard dg(h->gpu.device);
+    const size_t nr = h->rs->num_roots, w = size + nr;
+    const size_t eb = positions ? nr : 0;
+    const size_t chunk = std::max<size_t>(1, std::min(count, kRepHostBytes / (w + eb + 4 + 2 * nr)));
+    auto o_pos = [&](size_t n) { return rs_ws_round16(n * w); };
+    auto o_cnt = [&](size_t n) { return o_pos(n) + n * eb; };
+    auto o_ok = [&](size_t n) { return o_cnt(n) + n; };
+    auto o_cor = [&](size_t n) { return o_ok(n) + n; };
+    auto o_num = [&](size_t n) { return o_cor(n) + n; };
+    auto o_ep = [&](size_t n) { return rs_ws_round16(o_num(n) + n); };
+    auto o_ev = [&](size_t n) { return o_ep(n) + n * nr; };
+    GpuCtx::PipeSlot &ps = h->gpu.rslot;
+    if (!pipe_slot(h, ps, o_ev(chunk) + chunk * nr))
+        return false;
+    for (size_t c0 = 0; c0 < count; c0 += chunk) {
+        const size_t n = std::min(chunk, count - c0);
+        copy_rows(ps.host, w, data + c0 * data_stride, data_stride, size, n);
+        copy_rows(ps.host + size, w, parity + c0 * parity_stride, parity_stride, nr, n);
+        if (positions) {
+            copy_rows(ps.host + o_pos(n), nr, positions + c0 * positions_stride, positions_stride, nr, n);
+            memcpy(ps.host + o_cnt(n), counts + c0, n);
+        }
+        const RepOut d = {ps.dev + o_num(n), ps.dev + o_ep(n), ps.dev + o_ev(n), nr};
+        const bool good =
+            hipMemcpyAsync(ps.dev, ps.host, o_ok(n), hipMemcpyHostToDevice, ps.stream) == hipSuccess &&
+            rep_run(h, ps.dev, w, ps.dev + size, w, size, n, positions ? ps.dev + o_pos(n) : nullptr, nr,
+                    ps.dev + o_cnt(n), ps.dev + o_ok(n), ps.dev + o_cor(n), d, ps.stream) &&
+            hipMemcpyAsync(ps.host, ps.dev, n * w, hipMemcpyDeviceToHost, ps.stream) == hipSuccess &&
+            hipMemcpyAsync(ps.host + o_ok(n), ps.dev + o_ok(n), o_ev(n) + n * nr - o_ok(n), hipMemcpyDeviceToHost,
+                           ps.stream) == hipSuccess;
+        if (!good || hipStreamSynchronize(ps.stream) != hipSuccess) {
+            const std::string msg =
+                g_last_error.empty() ? std::string("HIP failure in a report host batch") : g_last_error;
+            (void)hipStreamSynchronize(ps.stream);
+            return fail("%s", msg.c_str());
+        }
+        copy_rows(data + c0 * data_stride, data_stride, ps.host, w, size, n);
+        copy_rows(parity + c0 * parity_stride, parity_stride, ps.host + size, w, nr, n);
+        memcpy(ok + c0, ps.host + o_ok(n), n);
+        if (corrected)
+            memcpy(corrected + c0, ps.host + o_cor(n), n);
+        memcpy(err_num + c0, ps.host + o_num(n), n);
+        copy_rows(err_pos + c0 * report_stride, report_stride, ps.host + o_ep(n), nr, nr, n);
+        copy_rows(err_val + c0 * report_stride, report_stride, ps.host + o_ev(n), nr, nr, n);
+    }
+    return true;
+}
+
+EXPORT bool poporon_amd_erasures_from_mask_device(poporon_t *h, const uint8_t *d_mask, size_t mask_stride, size_t size,
+                                                  size_t depth, size_t count, uint8_t *d_positions,
+                                                  size_t positions_stride, uint8_t *d_counts, uint8_t *d_over,
+                                                  void *stream)
+{
+    const char *what = "poporon_amd_erasures_from_mask_device";
+    if (!h)
+        return fail("%s: NULL handle", what);
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("%s serves RS handles", what);
+    if (count && (!d_mask || !d_positions || !d_counts))
+        return fail("%s: NULL argument", what);
+    if (depth < 1 || depth > RS_ILV_MAX_DEPTH)
+        return fail("%s: depth %zu outside [1, %u]", what, depth, (unsigned)RS_ILV_MAX_DEPTH);
+    if (!check_decode_size(h, size))
+        return fail("%s: size %zu outside [1, %u]", what, size, (unsigned)kmax(h));
+    const uint32_t nr = h->rs->num_roots;
+    if (mask_stride < size * depth)
+        return fail("%s: mask_stride %zu < size * depth = %zu", what, mask_stride, size * depth);
+    if (positions_stride < nr)
+        return fail("%s: positions_stride %zu < num_roots (%u)", what, positions_stride, (unsigned)nr);
+    if (count == 0)
+        return true;
+    if (!batch_enter(h))
+        return false;
+    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
+    DeviceGuard dg(h->gpu.device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t step = (size_t)1 << 24; /* frames per launch: frames * depth stays below 2^31 */
+    for (size_t f0 = 0; f0 < count; f0 += step) {
+        const size_t n = std::min(step, count - f0), c0 = f0 * depth;
+        KernelTimer t(h->gpu, POPORON_AMD_KERNEL_MASK_LISTS, s);
+        HIP_OK(rsk_mask_lists(d_mask + f0 * mask_stride, mask_stride, (uint32_t)size, (uint32_t)depth, nr, n,
+                              d_positions + c0 * positions_stride, positions_stride, d_counts + c0,
+                              d_over ? d_over + c0 : nullptr, s));
+        t.done();
+    }
+    return true;
 }
 
 /* ------------------------------------------------------------------------ */

@@ -415,6 +415,32 @@ hipError_t rsk_ilv_scatter(const uint8_t *rows, uint8_t *data, size_t dstride, u
                            uint32_t size, uint32_t nr, uint32_t depth, size_t nframes, bool with_data,
                            hipStream_t stream);
 
+/*
+ * Reports and erasure lists (rs_report.hip): the sparse non-zero bytes of a
+ * codeword-shaped region as an ascending list of at most nr entries per
+ * codeword, the slots behind the count 0, bytes nr .. stride never written.
+ *   rsk_snapshot    rows (data / parity, any strides) -> wire rows, size + nr
+ *                   bytes back to back, at snap (16-byte aligned, RS_ILV_ROW
+ *                   bytes per codeword allocated, at least 64 codewords)
+ *   rsk_report      rows now against the snapshot: num[c] changed bytes, their
+ *                   positions (0 .. size - 1 message, size .. parity) and
+ *                   snapshot ^ now at pos / val + c * rstride
+ *   rsk_mask_lists  flag plane (frame f at mask + f * mstride, symbol j of
+ *                   codeword i at j * depth + i, non-zero = flagged) -> for
+ *                   codeword c = f * depth + i the first nr flagged symbols at
+ *                   pos + c * pstride, cnt[c] = min(flagged, nr), over[c]
+ *                   (may be NULL) = flagged > nr
+ * size + nr <= 255; count and nframes * depth below 2^31.
+ */
+hipError_t rsk_snapshot(const uint8_t *data, size_t ds, const uint8_t *parity, size_t ps, uint8_t *snap, uint32_t size,
+                        uint32_t nr, size_t count, hipStream_t stream);
+hipError_t rsk_report(const uint8_t *data, size_t ds, const uint8_t *parity, size_t ps, const uint8_t *snap,
+                      uint32_t size, uint32_t nr, size_t count, uint8_t *num, uint8_t *pos, uint8_t *val,
+                      size_t rstride, hipStream_t stream);
+hipError_t rsk_mask_lists(const uint8_t *mask, size_t mstride, uint32_t size, uint32_t depth, uint32_t nr,
+                          size_t nframes, uint8_t *pos, size_t pstride, uint8_t *cnt, uint8_t *over,
+                          hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
