@@ -1462,6 +1462,27 @@ static bool check_decode_size(const poporon_t *h, size_t size)
     return size >= 1 && size <= kmax(h);
 }
 
+/* what every row decode entry point (host or device pointers) checks before
+ * it touches the GPU; rs_only: the report calls, which serve RS handles alone */
+static bool decode_row_args(const poporon_t *h, const char *what, bool rs_only, const uint8_t *data,
+                            const uint8_t *parity, size_t size, size_t count, const uint8_t *positions,
+                            size_t positions_stride, const uint8_t *counts, const uint8_t *ok)
+{
+    if (!h)
+        return fail("%s: NULL handle", what);
+    if (rs_only && h->fec_type != PPLN_FEC_RS)
+        return fail("%s serves RS handles", what);
+    if (is_ldpc(h, what))
+        return false;
+    if (count && (!data || !parity || !ok))
+        return fail("%s: NULL argument", what);
+    if (positions && (h->fec_type != PPLN_FEC_RS || !counts || positions_stride < h->rs->num_roots))
+        return fail("%s: erasure batch needs an RS handle, counts and positions_stride >= num_roots", what);
+    if (!check_decode_size(h, size))
+        return fail("%s: decode size %zu outside [1, %u]", what, size, (unsigned)kmax(h));
+    return true;
+}
+
 /* ------------------------------------------------------------------------ */
 /* in-library kernel timing (HIP events on the launch stream)               */
 /* ------------------------------------------------------------------------ */
@@ -1515,6 +1536,15 @@ struct KernelTimer {
     }
     ~KernelTimer() { done(false); }
 };
+
+/* One stage: the launches of CALL timed under ID on stream S.  A failed launch
+ * returns false from the enclosing function, its events back in the pool unread. */
+#define STAGE(G, ID, S, CALL)                                                                                         \
+    do {                                                                                                              \
+        KernelTimer t_((G), (ID), (S));                                                                               \
+        HIP_OK(CALL);                                                                                                 \
+        t_.done();                                                                                                    \
+    } while (0)
 
 /* Folds the finished stage timings into the totals.  An entry whose events
  * cannot be read is dropped (its events recycled) rather than left queued,
@@ -1619,6 +1649,24 @@ static bool gen_wave(const poporon_t *h, size_t count, bool encode, size_t size)
     return count < 16384 || (encode ? nn == 255u : nn >= 15u);
 }
 
+/* the handle's kernel parameters for rows of `size` message bytes (a shortened
+ * code: pad = nn - num_roots - size virtual zeros in front; only decodes read it) */
+static RsCorrParams corr_params(const poporon_t *h, size_t size)
+{
+    RsCorrParams prm = h->corr;
+    prm.size = (uint32_t)size;
+    prm.pad = (int32_t)(h->rs->gf->field_size - h->rs->num_roots - size);
+    return prm;
+}
+
+static RsGenParams gen_params(const poporon_t *h, size_t size)
+{
+    RsGenParams prm = h->gen;
+    prm.size = (uint32_t)size;
+    prm.pad = (int32_t)(h->rs->gf->field_size - h->rs->num_roots - size);
+    return prm;
+}
+
 #define GEN_LFSR_MIN 1024 /* batch size from which codes of more than 32 roots encode on rsg_lfsr_k */
 
 static bool launch_encode(poporon_t *h, const uint8_t *d_data, size_t ds, uint8_t *d_par, size_t ps, size_t size,
@@ -1643,12 +1691,10 @@ static bool launch_encode(poporon_t *h, const uint8_t *d_data, size_t ds, uint8_
          * batches on the wave kernel, whose codeword spreads over the wave:
          * 64 codewords 27-34 vs 34-41 us, 4,096 39-53 vs 51-53 -> 39-45,
          * 65,536 292-524 vs 43-52 us, profiles/r06_general_lat_auto_v2.log) */
-        RsGenParams prm = h->gen;
-        prm.size = (uint32_t)size;
+        const RsGenParams prm = gen_params(h, size);
         HIP_OK(rsg_lfsr_encode(h->gpu.gtab, &prm, d_data, ds, d_par, ps, count, h->gpu.num_cu, s));
     } else {
-        RsGenParams prm = h->gen;
-        prm.size = (uint32_t)size;
+        const RsGenParams prm = gen_params(h, size);
         if (gen_wave(h, count, true, size))
             HIP_OK(rsgw_encode(h->gpu.gtab, &prm, d_data, ds, d_par, ps, count, nullptr, 0u, h->gpu.num_cu, s));
         else
@@ -1665,348 +1711,322 @@ static bool launch_encode(poporon_t *h, const uint8_t *d_data, size_t ds, uint8_
  * ~108, 32,768 196 vs ~110 */
 #define SPLIT_MIN_COUNT 16384
 
-/* the split error-mode decode of one sub-batch (rs_fast.hip); npar < 32: a
- * byte-symbol code of npar roots (h->nrsplit), its list on the general kernel */
-static bool launch_split(poporon_t *h, const RsCorrParams &prm, const RsSplitWs &ws, uint8_t *d_data, size_t ds,
-                         uint8_t *d_par, size_t ps, size_t size, size_t count, uint8_t *ok, uint8_t *corrected,
-                         hipStream_t s, uint32_t npar = RS_NR, const uint16_t *ext = nullptr, size_t ext_stride = 0)
+/* One batch decode, as every entry point describes it (device pointers) */
+struct DecodeCall {
+    uint8_t *data;
+    size_t ds;
+    uint8_t *par;
+    size_t ps;
+    size_t size, count;
+    const uint16_t *ext_syn; /* external log-form syndromes (src/decode.c:446-464); NULL: the rows' own */
+    size_t ext_stride;
+    const uint8_t *pos8; /* erasure slots as u8 or as u32 (never both; neither: errors only), */
+    const uint32_t *pos32;
+    size_t pos_stride;  /* pos_stride elements apart, */
+    const uint8_t *cnt; /* and how many of each row's slots count */
+    uint8_t *ok, *corrected;
+    hipStream_t s;
+    uint8_t *rem; /* the caller's workspace of rs_ws_bytes(rem_cap) bytes, rem_cap >= count; NULL: the handle's */
+    size_t rem_cap;
+};
+
+enum DecodeRoute {
+    ROUTE_BCH,        /* bchk_decode */
+    ROUTE_SINGLE,     /* one codeword on one workgroup (rsk_decode1): 32 roots or fewer, every mode */
+    ROUTE_GENERAL,    /* general parameters: one codeword per wave or per lane (rsgw_decode / rsg_decode) */
+    ROUTE_WAVE,       /* one codeword per wave, syndromes included, one launch (rsk_wave) */
+    ROUTE_SPLIT,      /* errors only, the rows' syndromes or external ones: the split kernels (launch_split) */
+    ROUTE_ERRATA,     /* u8 erasure slots in 4-byte aligned rows: the errata kernels (launch_errata) */
+    ROUTE_ERA_ERRATA, /* ... in 16-byte aligned rows, prim 1: rsk_era first, the errata kernels for what it leaves */
+    ROUTE_ERA,        /* ... rsk_era alone (rows the errata kernels cannot read) */
+    ROUTE_ERA_RECORD, /* any other erasure slots: rsk_correct_era_rec, its records applied block-wise */
+    ROUTE_CORRECT     /* the rest: the single kernel over the whole batch (rsk_correct) */
+};
+
+/* Does the batch take the lane-per-codeword kernels (rs_fast.hip, rs_errata.hip)?
+ * RS(255,223): from SPLIT_MIN_COUNT codewords on.  A byte-symbol code of fewer
+ * than 32 roots: at every batch size, single calls included -- the general
+ * kernel's one lane per codeword takes ~1 ms whatever the count, the six split
+ * launches ~0.1 ms from 1 to 65,536 codewords of RS(255,239)
+ * (profiles/r05_nr_batchlat.log). */
+static bool split_ok(const poporon_t *h, size_t count)
 {
-    GpuCtx &g = h->gpu;
-    const bool nr = npar < RS_NR;
-    {
-        KernelTimer t(g, POPORON_AMD_KERNEL_REMAINDER, s);
-        if (ext) /* external log-form syndromes (src/decode.c:446-464): converted, refusals to the list */
-            HIP_OK(rsk_ext_syn(g.tab, ext, ext_stride, count, npar, ws.syn, ws.list, ws.nlist, s));
-        else if (nr)
-            HIP_OK(rsk_syndrome_reset_nr(g.tab, d_data, ds, d_par, ps, (uint32_t)size, count, ws.syn, ws.nlist, npar,
-                                         g.num_cu, s));
-        else
-            HIP_OK(rsk_syndrome_reset(g.tab, d_data, ds, d_par, ps, (uint32_t)size, count, ws.syn, ws.nlist,
-                                      g.num_cu, s));
-        t.done();
-    }
-    {
-        KernelTimer t(g, POPORON_AMD_KERNEL_BM, s);
-        if (nr)
-            HIP_OK(rsk_bm_nr(g.tab, &ws, count, npar, ok, corrected, g.num_cu, s));
-        else
-            HIP_OK(rsk_bm(g.tab, &ws, count, ok, corrected, g.num_cu, s));
-        t.done();
-    }
-    {
-        KernelTimer t(g, POPORON_AMD_KERNEL_CHIEN, s);
-        HIP_OK(rsk_chien(g.tab, &prm, &ws, count, ok, corrected, g.num_cu, s));
-        t.done();
-    }
-    if (h->decode_tail == 0) {
-        /* Forney and the block apply in one kernel (rs_forney_apply_k), charged to the apply's id */
-        KernelTimer t(g, POPORON_AMD_KERNEL_APPLY, s);
-        HIP_OK(rsk_forney_apply(g.tab, &prm, &ws, d_data, ds, d_par, ps, count, npar, ok, corrected, g.num_cu, s));
-        t.done();
-    } else {
-        {
-            KernelTimer t(g, POPORON_AMD_KERNEL_FORNEY, s);
-            HIP_OK(rsk_forney(g.tab, &prm, &ws, d_data, ds, d_par, ps, count, ok, corrected, g.num_cu, s));
-            t.done();
-        }
-        {
-            KernelTimer t(g, POPORON_AMD_KERNEL_APPLY, s);
-            if (nr)
-                HIP_OK(rsk_apply_nr(&prm, &ws, d_data, ds, d_par, ps, count, npar, s));
-            else
-                HIP_OK(rsk_apply(&prm, &ws, d_data, ds, d_par, ps, count, s));
-            t.done();
-        }
-    }
-    {
-        /* what the split kernels hand on: one codeword per wave (rs_wave_k) */
-        KernelTimer t(g, POPORON_AMD_KERNEL_LIST, s);
-        if (nr) {
-            RsGenParams gp = h->gen;
-            gp.size = (uint32_t)size;
-            gp.pad = prm.pad;
-            if (h->gen_path == 1)
-                HIP_OK(rsg_decode_list(g.gtab, &gp, d_data, ds, d_par, ps, count, ws.list, ws.nlist, ext, ext_stride,
-                                       nullptr, 0, nullptr, ok, corrected, g.num_cu, s));
-            else
-                HIP_OK(rsgw_decode(g.gtab, &gp, d_data, ds, d_par, ps, count, ext, ext_stride, nullptr, nullptr, 0,
-                                   nullptr, ok, corrected, ws.list, ws.nlist, nullptr, 0u, g.num_cu, s));
-        } else {
-            HIP_OK(rsk_wave(g.tab, &prm, d_data, ds, d_par, ps, count, ws.list, ws.nlist, ext ? nullptr : ws.syn, ext,
-                            ext_stride, nullptr, nullptr, 0, nullptr, ok, corrected, g.num_cu, s));
-        }
-        t.done();
-    }
-    return true;
+    if (!h->corr.vfast || h->corr.force_verify)
+        return false;
+    if (h->nrsplit)
+        return h->decode_path == 0 || h->decode_path == 1;
+    return h->decode_path != 2 && (h->decode_path == 1 || count >= SPLIT_MIN_COUNT);
 }
 
-/* rem / rem_cap: a workspace of rs_ws_bytes(rem_cap) bytes (rem_cap >= count)
- * owned by the caller; NULL: the handle's own */
-static bool launch_decode(poporon_t *h, uint8_t *d_data, size_t ds, uint8_t *d_par, size_t ps, size_t size,
-                          size_t count, const uint16_t *ext_syn, size_t ext_stride, const uint8_t *pos8,
-                          const uint32_t *pos32, size_t pos_stride, const uint8_t *cnt, uint8_t *ok,
-                          uint8_t *corrected, hipStream_t s, uint8_t *rem = nullptr, size_t rem_cap = 0)
+/* Which kernels decode the call: decided here and nowhere else, from the
+ * handle and the call alone (no HIP call, no side effect).  The order of the
+ * tests is the dispatch. */
+static DecodeRoute decode_route(const poporon_t *h, const DecodeCall &c)
 {
-    if (h->fec_type == PPLN_FEC_BCH) {
-        if (ext_syn || pos8 || pos32)
-            return fail("BCH has no erasure or external-syndrome decode");
-        KernelTimer t(h->gpu, POPORON_AMD_KERNEL_CORRECT, s);
-        HIP_OK(bchk_decode(&h->bch, d_data, ds, d_par, ps, count, ok, corrected, h->gpu.num_cu, s));
-        t.done();
-        return true;
+    if (h->fec_type == PPLN_FEC_BCH)
+        return ROUTE_BCH;
+    const bool era = c.pos8 || c.pos32;
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(c.pos8);
+    /* u8 slots in rows the errata kernels read word by word */
+    const bool rows4 = c.pos8 && c.pos_stride >= h->rs->num_roots && c.pos_stride % 4u == 0u && (pa & 3u) == 0u;
+    if (h->nrsplit) {
+        if (c.count == 1 && h->decode_path == 0)
+            return ROUTE_SINGLE;
+        if (!era && split_ok(h, c.count))
+            return ROUTE_SPLIT;
+        if (rows4 && !c.ext_syn && split_ok(h, c.count))
+            return ROUTE_ERRATA;
     }
-    if (h->nrsplit && count == 1 && h->decode_path == 0) {
-        /* one codeword of a fewer-roots code: the whole reference decode on
-         * one workgroup (rs_dec1_k with P.nr = num_roots; every mode) */
-        RsCorrParams prm = h->corr;
-        prm.size = (uint32_t)size;
-        prm.pad = (int32_t)(h->rs->gf->field_size - h->rs->num_roots - size);
-        KernelTimer t(h->gpu, POPORON_AMD_KERNEL_SINGLE, s);
-        HIP_OK(rsk_decode1(h->gpu.tab, &prm, ext_syn ? 2u : (pos8 || pos32) ? 1u : 0u, d_data, d_par, pos8, pos32,
-                           cnt, 1u, ext_syn, ok, corrected, nullptr, 0, s));
-        t.done();
-        return true;
-    }
-    if (h->nrsplit && !pos8 && !pos32 && h->corr.vfast && !h->corr.force_verify &&
-        (h->decode_path == 1 || h->decode_path == 0)) {
-        /* a byte-symbol code of fewer than 32 roots, errors only: the split
-         * kernels with npar = num_roots, the list on the general kernel --
-         * at every batch size, single calls included: the general kernel's
-         * one lane per codeword takes ~1 ms whatever the count, the six
-         * split launches ~0.1 ms from 1 to 65,536 codewords of RS(255,239)
-         * (profiles/r05_nr_batchlat.log) */
-        RsCorrParams prm = h->corr;
-        prm.size = (uint32_t)size;
-        prm.pad = (int32_t)(h->rs->gf->field_size - h->rs->num_roots - size);
-        const bool shared = !rem;
-        if (shared) {
-            if (!ensure_rem(h, count) || !rem_acquire(h->gpu, s))
-                return false;
-            rem = h->gpu.rem;
-            rem_cap = h->gpu.rem_cap;
-        }
-        const RsSplitWs ws = rs_ws_carve(rem, rem_cap ? rem_cap : count);
-        if (!launch_split(h, prm, ws, d_data, ds, d_par, ps, size, count, ok, corrected, s, h->rs->num_roots, ext_syn,
-                          ext_stride))
-            return false;
-        return !shared || rem_release(h->gpu, s);
-    }
-    if (h->nrsplit && pos8 && !ext_syn && h->corr.vfast && !h->corr.force_verify &&
-        (h->decode_path == 1 || h->decode_path == 0) && pos_stride >= h->rs->num_roots && pos_stride % 4u == 0u &&
-        (reinterpret_cast<uintptr_t>(pos8) & 3u) == 0u) {
-        /* ... and its erasure batches (u8 slots in 4-byte aligned rows): the
-         * errata kernels with npar = num_roots, the list on the general
-         * kernel in erasure mode, the 32-entry record apply */
-        const uint32_t nr = h->rs->num_roots;
-        RsCorrParams prm = h->corr;
-        prm.size = (uint32_t)size;
-        prm.pad = (int32_t)(h->rs->gf->field_size - nr - size);
-        GpuCtx &g = h->gpu;
-        const bool shared = !rem;
-        if (shared) {
-            if (!ensure_rem(h, count) || !rem_acquire(g, s))
-                return false;
-            rem = g.rem;
-            rem_cap = g.rem_cap;
-        }
-        const RsSplitWs ws = rs_ws_carve(rem, rem_cap ? rem_cap : count);
-        {
-            KernelTimer t(g, POPORON_AMD_KERNEL_REMAINDER, s);
-            HIP_OK(rsk_syndrome_reset_nr(g.tab, d_data, ds, d_par, ps, (uint32_t)size, count, ws.syn, ws.nlist, nr,
-                                         g.num_cu, s));
-            t.done();
-        }
-        {
-            KernelTimer t(g, POPORON_AMD_KERNEL_BM, s);
-            HIP_OK(rsk_ebm_nr(g.tab, &prm, &ws, pos8, pos_stride, cnt, count, ok, corrected, nr, g.num_cu, s));
-            t.done();
-        }
-        {
-            KernelTimer t(g, POPORON_AMD_KERNEL_CHIEN, s);
-            HIP_OK(rsk_chien32(g.tab, &prm, &ws, count, ok, corrected, 0u, g.num_cu, s));
-            t.done();
-        }
-        {
-            KernelTimer t(g, POPORON_AMD_KERNEL_FORNEY, s);
-            HIP_OK(rsk_forney32_nr(g.tab, &prm, &ws, pos8, pos_stride, count, ok, corrected, nr, g.num_cu, s));
-            t.done();
-        }
-        {
-            /* the hand-off (meta RS_ST_LIST: the record apply passes them by) */
-            KernelTimer t(g, POPORON_AMD_KERNEL_LIST, s);
-            RsGenParams gp = h->gen;
-            gp.size = (uint32_t)size;
-            gp.pad = prm.pad;
-            if (h->gen_path == 1)
-                HIP_OK(rsg_decode_list(g.gtab, &gp, d_data, ds, d_par, ps, count, ws.list, ws.nlist, nullptr, 0, pos8,
-                                       pos_stride, cnt, ok, corrected, g.num_cu, s));
-            else
-                HIP_OK(rsgw_decode(g.gtab, &gp, d_data, ds, d_par, ps, count, nullptr, 0, pos8, nullptr, pos_stride,
-                                   cnt, ok, corrected, ws.list, ws.nlist, nullptr, 0u, g.num_cu, s));
-            t.done();
-        }
-        {
-            KernelTimer t(g, POPORON_AMD_KERNEL_APPLY, s);
-            HIP_OK(rsk_apply_era_nr(&prm, ws.meta, ws.ext, d_data, ds, d_par, ps, count, nr, s));
-            t.done();
-        }
-        return !shared || rem_release(g, s);
-    }
-    if (!h->fast) {
-        RsGenParams prm = h->gen;
-        prm.size = (uint32_t)size;
-        prm.pad = (int32_t)(h->rs->gf->field_size - h->rs->num_roots - size);
-        KernelTimer t(h->gpu, POPORON_AMD_KERNEL_CORRECT, s);
-        if (gen_wave(h, count, false, size))
-            HIP_OK(rsgw_decode(h->gpu.gtab, &prm, d_data, ds, d_par, ps, count, ext_syn, ext_stride, pos8, pos32,
-                               pos_stride, cnt, ok, corrected, nullptr, nullptr, nullptr, 0u, h->gpu.num_cu, s));
-        else
-            HIP_OK(rsg_decode(h->gpu.gtab, &prm, d_data, ds, d_par, ps, count, ext_syn, ext_stride, pos8, pos32,
-                              pos_stride, cnt, ok, corrected, h->gpu.num_cu, s));
-        t.done();
-        return true;
-    }
-    RsCorrParams prm = h->corr;
-    prm.size = (uint32_t)size;
-    prm.pad = (int32_t)(h->rs->gf->field_size - h->rs->num_roots - size);
-    if (count == 1) { /* one codeword: one launch on one workgroup (rs_single.hip; it always runs the check) */
-        KernelTimer t(h->gpu, POPORON_AMD_KERNEL_SINGLE, s);
-        HIP_OK(rsk_decode1(h->gpu.tab, &prm, ext_syn ? 2u : (pos8 || pos32) ? 1u : 0u, d_data, d_par, pos8, pos32,
-                           cnt, 1u, ext_syn, ok, corrected, nullptr, 0, s));
-        t.done();
-        return true;
-    }
-    /* a few thousand codewords: one codeword per wave, syndromes included,
-     * one launch (the lane-per-codeword kernels would give each SIMD a few
-     * waves, each a ~10^4-step serial chain) */
-    if (h->decode_path == 3 || (h->decode_path == 0 && count < SPLIT_MIN_COUNT)) {
-        KernelTimer t(h->gpu, POPORON_AMD_KERNEL_WAVE, s);
-        HIP_OK(rsk_wave(h->gpu.tab, &prm, d_data, ds, d_par, ps, count, nullptr, nullptr, nullptr, ext_syn, ext_stride,
-                        pos8, pos32, pos_stride, cnt, ok, corrected, h->gpu.num_cu, s));
-        t.done();
-        return true;
-    }
-    /* external syndromes of a large batch: the split kernels from converted
-     * syndromes, refusals and what they hand on to rs_wave_k (which reads
-     * the external syndromes itself) */
-    const bool xsplit = ext_syn && !pos8 && !pos32 && prm.vfast && !prm.force_verify && h->decode_path != 2 &&
-                        (h->decode_path == 1 || count >= SPLIT_MIN_COUNT);
-    if (xsplit) {
-        const bool own = !rem;
-        if (own) {
-            if (!ensure_rem(h, count) || !rem_acquire(h->gpu, s))
-                return false;
-            rem = h->gpu.rem;
-            rem_cap = h->gpu.rem_cap;
-        }
-        const RsSplitWs ws = rs_ws_carve(rem, rem_cap ? rem_cap : count);
-        if (!launch_split(h, prm, ws, d_data, ds, d_par, ps, size, count, ok, corrected, s, RS_NR, ext_syn,
-                          ext_stride))
-            return false;
-        return !own || rem_release(h->gpu, s);
-    }
-    const bool shared = !rem && !ext_syn; /* the handle's workspace */
-    if (shared) {
+    if (!h->fast)
+        return ROUTE_GENERAL;
+    if (c.count == 1)
+        return ROUTE_SINGLE;
+    /* a few thousand codewords: the lane-per-codeword kernels would give each
+     * SIMD a few waves, each a ~10^4-step serial chain */
+    if (h->decode_path == 3 || (h->decode_path == 0 && c.count < SPLIT_MIN_COUNT))
+        return ROUTE_WAVE;
+    if (!split_ok(h, c.count))
+        return ROUTE_CORRECT;
+    if (!era)
+        return ROUTE_SPLIT;
+    if (c.ext_syn)
+        return ROUTE_CORRECT;
+    /* u8 slots: rs_era_bp_k for 32 sorted erasures (prim 1, rows read as
+     * uint4), the errata kernels for every other count with or without errors;
+     * u32 slots and unaligned rows: the record kernel for all */
+    if (c.pos8 && h->corr.prim == 1u && c.pos_stride % 16u == 0u && (pa & 15u) == 0u)
+        return rows4 ? ROUTE_ERA_ERRATA : ROUTE_ERA;
+    return rows4 ? ROUTE_ERRATA : ROUTE_ERA_RECORD;
+}
+
+/* The workspace of one call: the caller's if it brought one, else the handle's
+ * (grown to the count and ordered behind its last reader on another stream).
+ * ws_release after the call's last reader -- never on an error return, which
+ * leaves rem_done unrecorded. */
+struct DecodeWs {
+    uint8_t *rem = nullptr;
+    bool shared = false;
+    RsSplitWs ws = {};
+};
+
+static bool ws_acquire(poporon_t *h, uint8_t *rem, size_t rem_cap, size_t count, hipStream_t s, DecodeWs &w)
+{
+    w.shared = !rem;
+    if (w.shared) {
         if (!ensure_rem(h, count) || !rem_acquire(h->gpu, s))
             return false;
         rem = h->gpu.rem;
         rem_cap = h->gpu.rem_cap;
     }
-    const bool split = !ext_syn && !pos8 && !pos32 && prm.vfast && !prm.force_verify &&
-                       h->decode_path != 2 && (h->decode_path == 1 || count >= SPLIT_MIN_COUNT);
-    if (split) {
-        const RsSplitWs ws = rs_ws_carve(rem, rem_cap ? rem_cap : count);
-        GpuCtx &g = h->gpu;
-        /* (sub-batches of 2^19 codewords, to keep a sub-batch's bytes in the
-         * Infinity Cache until the apply, measured slower: 0.84 vs 0.75 ms
-         * per bench step) */
-        if (!launch_split(h, prm, ws, d_data, ds, d_par, ps, size, count, ok, corrected, s))
-            return false;
-        return !shared || rem_release(g, s);
+    w.rem = rem;
+    w.ws = rs_ws_carve(rem, rem_cap ? rem_cap : count);
+    return true;
+}
+
+static bool ws_release(poporon_t *h, const DecodeWs &w, hipStream_t s) { return !w.shared || rem_release(h->gpu, s); }
+
+/* what the lane-per-codeword kernels of a fewer-roots code hand on (ws.list):
+ * the general kernel, per lane or per wave, in the call's own mode */
+static hipError_t launch_list_nr(poporon_t *h, const DecodeCall &c, const RsSplitWs &ws)
+{
+    GpuCtx &g = h->gpu;
+    const RsGenParams gp = gen_params(h, c.size);
+    const size_t xs = c.ext_syn ? c.ext_stride : 0, es = c.pos8 ? c.pos_stride : 0;
+    const uint8_t *cnt = c.pos8 ? c.cnt : nullptr;
+    if (h->gen_path == 1)
+        return rsg_decode_list(g.gtab, &gp, c.data, c.ds, c.par, c.ps, c.count, ws.list, ws.nlist, c.ext_syn, xs,
+                               c.pos8, es, cnt, c.ok, c.corrected, g.num_cu, c.s);
+    return rsgw_decode(g.gtab, &gp, c.data, c.ds, c.par, c.ps, c.count, c.ext_syn, xs, c.pos8, nullptr, es, cnt, c.ok,
+                       c.corrected, ws.list, ws.nlist, nullptr, 0u, g.num_cu, c.s);
+}
+
+/* ROUTE_SPLIT: the split error-mode decode (rs_fast.hip, one codeword per
+ * lane; what it hands on: one codeword per wave); fewer than 32 roots: the
+ * _nr kernels, the list on the general kernel */
+static bool launch_split(poporon_t *h, const DecodeCall &c)
+{
+    GpuCtx &g = h->gpu;
+    hipStream_t s = c.s;
+    const uint32_t npar = h->rs->num_roots, size = (uint32_t)c.size;
+    const bool nr = npar < RS_NR;
+    const RsCorrParams prm = corr_params(h, c.size);
+    DecodeWs w;
+    if (!ws_acquire(h, c.rem, c.rem_cap, c.count, s, w))
+        return false;
+    const RsSplitWs &ws = w.ws;
+    /* (external syndromes: converted, refusals to the list) */
+    STAGE(g, POPORON_AMD_KERNEL_REMAINDER, s,
+          c.ext_syn ? rsk_ext_syn(g.tab, c.ext_syn, c.ext_stride, c.count, npar, ws.syn, ws.list, ws.nlist, s)
+          : nr      ? rsk_syndrome_reset_nr(g.tab, c.data, c.ds, c.par, c.ps, size, c.count, ws.syn, ws.nlist, npar,
+                                            g.num_cu, s)
+                    : rsk_syndrome_reset(g.tab, c.data, c.ds, c.par, c.ps, size, c.count, ws.syn, ws.nlist, g.num_cu,
+                                         s));
+    STAGE(g, POPORON_AMD_KERNEL_BM, s,
+          nr ? rsk_bm_nr(g.tab, &ws, c.count, npar, c.ok, c.corrected, g.num_cu, s)
+             : rsk_bm(g.tab, &ws, c.count, c.ok, c.corrected, g.num_cu, s));
+    STAGE(g, POPORON_AMD_KERNEL_CHIEN, s, rsk_chien(g.tab, &prm, &ws, c.count, c.ok, c.corrected, g.num_cu, s));
+    if (h->decode_tail == 0) {
+        /* Forney and the block apply in one kernel (rs_forney_apply_k), charged to the apply's id */
+        STAGE(g, POPORON_AMD_KERNEL_APPLY, s,
+              rsk_forney_apply(g.tab, &prm, &ws, c.data, c.ds, c.par, c.ps, c.count, npar, c.ok, c.corrected, g.num_cu,
+                               s));
+    } else {
+        STAGE(g, POPORON_AMD_KERNEL_FORNEY, s,
+              rsk_forney(g.tab, &prm, &ws, c.data, c.ds, c.par, c.ps, c.count, c.ok, c.corrected, g.num_cu, s));
+        STAGE(g, POPORON_AMD_KERNEL_APPLY, s,
+              nr ? rsk_apply_nr(&prm, &ws, c.data, c.ds, c.par, c.ps, c.count, npar, s)
+                 : rsk_apply(&prm, &ws, c.data, c.ds, c.par, c.ps, c.count, s));
     }
-    /* erasure batches: records (64 B per codeword in ws.ext) applied
-     * block-wise (scattered byte read-modify-writes cost ~0.3 ms per 2^20
-     * codewords with 32 erasures).  u8 slots: rs_era_bp_k for 32 sorted
-     * erasures (prim 1), the errata kernels (rs_errata.hip) for every other
-     * count with or without errors, the general kernel's list for what they
-     * hand on; u32 slots: the general kernel for all */
-    const bool esplit = !ext_syn && (pos8 || pos32) && prm.vfast && !prm.force_verify &&
-                        h->decode_path != 2 && (h->decode_path == 1 || count >= SPLIT_MIN_COUNT);
-    if (esplit) {
-        const RsSplitWs ws = rs_ws_carve(rem, rem_cap ? rem_cap : count);
-        GpuCtx &g = h->gpu;
-        const uintptr_t pa = reinterpret_cast<uintptr_t>(pos8);
-        const bool efast = pos8 && prm.prim == 1u && pos_stride % 16u == 0u && (pa & 15u) == 0u;
-        const bool errata = pos8 && pos_stride >= RS_NR && pos_stride % 4u == 0u && (pa & 3u) == 0u;
-        if (efast || errata) {
-            {
-                KernelTimer t(g, POPORON_AMD_KERNEL_REMAINDER, s);
-                HIP_OK(rsk_syndrome_reset(g.tab, d_data, ds, d_par, ps, (uint32_t)size, count, ws.syn, ws.nlist,
-                                          g.num_cu, s));
-                t.done();
-            }
-            if (efast) {
-                KernelTimer t(g, POPORON_AMD_KERNEL_ERASURE, s);
-                HIP_OK(rsk_era(g.tab, &prm, &ws, pos8, pos_stride, cnt, count, ok, corrected, errata ? 1u : 0u,
-                               g.num_cu, s));
-                t.done();
-            }
-            if (errata) {
-                const uint32_t only_pend = efast ? 1u : 0u;
-                {
-                    KernelTimer t(g, POPORON_AMD_KERNEL_BM, s);
-                    HIP_OK(rsk_ebm(g.tab, &prm, &ws, pos8, pos_stride, cnt, count, ok, corrected, only_pend, g.num_cu,
-                                   s));
-                    t.done();
-                }
-                {
-                    KernelTimer t(g, POPORON_AMD_KERNEL_CHIEN, s);
-                    HIP_OK(rsk_chien32(g.tab, &prm, &ws, count, ok, corrected, only_pend, g.num_cu, s));
-                    t.done();
-                }
-                {
-                    KernelTimer t(g, POPORON_AMD_KERNEL_FORNEY, s);
-                    HIP_OK(rsk_forney32(g.tab, &prm, &ws, pos8, pos_stride, count, ok, corrected, only_pend,
-                                        g.num_cu, s));
-                    t.done();
-                }
-            }
-            {
-                /* what those hand on: one codeword per wave, in place (their
-                 * meta stays RS_ST_LIST: the block apply passes them by) */
-                KernelTimer t(g, POPORON_AMD_KERNEL_LIST, s);
-                HIP_OK(rsk_wave(g.tab, &prm, d_data, ds, d_par, ps, count, ws.list, ws.nlist, ws.syn, nullptr, 0,
-                                pos8, nullptr, pos_stride, cnt, ok, corrected, g.num_cu, s));
-                t.done();
-            }
-        } else {
-            {
-                KernelTimer t(g, POPORON_AMD_KERNEL_REMAINDER, s);
-                HIP_OK(rsk_syndrome(g.tab, d_data, ds, d_par, ps, (uint32_t)size, count, ws.syn, g.num_cu, s));
-                t.done();
-            }
-            KernelTimer t(g, POPORON_AMD_KERNEL_CORRECT, s);
-            HIP_OK(rsk_correct_era_rec(g.tab, &prm, count, ws.syn, pos8, pos32, pos_stride, cnt, ok, corrected, ws.ext,
-                                       ws.meta, g.num_cu, s));
-            t.done();
-        }
-        {
-            KernelTimer t(g, POPORON_AMD_KERNEL_APPLY, s);
-            HIP_OK(rsk_apply_era(&prm, ws.meta, ws.ext, d_data, ds, d_par, ps, count, s));
-            t.done();
-        }
-        return !shared || rem_release(g, s);
+    STAGE(g, POPORON_AMD_KERNEL_LIST, s,
+          nr ? launch_list_nr(h, c, ws)
+             : rsk_wave(g.tab, &prm, c.data, c.ds, c.par, c.ps, c.count, ws.list, ws.nlist,
+                        c.ext_syn ? nullptr : ws.syn, c.ext_syn, c.ext_syn ? c.ext_stride : 0, nullptr, nullptr, 0,
+                        nullptr, c.ok, c.corrected, g.num_cu, s));
+    return ws_release(h, w, s);
+}
+
+/* ROUTE_ERRATA / ROUTE_ERA_ERRATA / ROUTE_ERA: erasure batches in u8 slots.
+ * Records (64 B per codeword in ws.ext) applied block-wise: scattered byte
+ * read-modify-writes cost ~0.3 ms per 2^20 codewords with 32 erasures.  What
+ * the kernels hand on stays RS_ST_LIST in ws.meta: decoded in place by the
+ * list kernel, passed by in the record apply.  Fewer than 32 roots: the _nr
+ * kernels (never rsk_era), the list on the general kernel in erasure mode. */
+static bool launch_errata(poporon_t *h, const DecodeCall &c, bool era_first, bool errata)
+{
+    GpuCtx &g = h->gpu;
+    hipStream_t s = c.s;
+    const uint32_t npar = h->rs->num_roots, size = (uint32_t)c.size;
+    const bool nr = npar < RS_NR;
+    const uint32_t only_pend = era_first ? 1u : 0u; /* the errata kernels take what rsk_era left pending */
+    const RsCorrParams prm = corr_params(h, c.size);
+    DecodeWs w;
+    if (!ws_acquire(h, c.rem, c.rem_cap, c.count, s, w))
+        return false;
+    const RsSplitWs &ws = w.ws;
+    STAGE(g, POPORON_AMD_KERNEL_REMAINDER, s,
+          nr ? rsk_syndrome_reset_nr(g.tab, c.data, c.ds, c.par, c.ps, size, c.count, ws.syn, ws.nlist, npar, g.num_cu,
+                                     s)
+             : rsk_syndrome_reset(g.tab, c.data, c.ds, c.par, c.ps, size, c.count, ws.syn, ws.nlist, g.num_cu, s));
+    if (era_first)
+        STAGE(g, POPORON_AMD_KERNEL_ERASURE, s,
+              rsk_era(g.tab, &prm, &ws, c.pos8, c.pos_stride, c.cnt, c.count, c.ok, c.corrected, errata ? 1u : 0u,
+                      g.num_cu, s));
+    if (errata) {
+        STAGE(g, POPORON_AMD_KERNEL_BM, s,
+              nr ? rsk_ebm_nr(g.tab, &prm, &ws, c.pos8, c.pos_stride, c.cnt, c.count, c.ok, c.corrected, npar,
+                              g.num_cu, s)
+                 : rsk_ebm(g.tab, &prm, &ws, c.pos8, c.pos_stride, c.cnt, c.count, c.ok, c.corrected, only_pend,
+                           g.num_cu, s));
+        STAGE(g, POPORON_AMD_KERNEL_CHIEN, s,
+              rsk_chien32(g.tab, &prm, &ws, c.count, c.ok, c.corrected, only_pend, g.num_cu, s));
+        STAGE(g, POPORON_AMD_KERNEL_FORNEY, s,
+              nr ? rsk_forney32_nr(g.tab, &prm, &ws, c.pos8, c.pos_stride, c.count, c.ok, c.corrected, npar, g.num_cu,
+                                   s)
+                 : rsk_forney32(g.tab, &prm, &ws, c.pos8, c.pos_stride, c.count, c.ok, c.corrected, only_pend,
+                                g.num_cu, s));
     }
-    if (!ext_syn) {
-        KernelTimer t(h->gpu, POPORON_AMD_KERNEL_REMAINDER, s);
-        HIP_OK(rsk_syndrome(h->gpu.tab, d_data, ds, d_par, ps, (uint32_t)size, count, rem, h->gpu.num_cu, s));
-        t.done();
+    STAGE(g, POPORON_AMD_KERNEL_LIST, s,
+          nr ? launch_list_nr(h, c, ws)
+             : rsk_wave(g.tab, &prm, c.data, c.ds, c.par, c.ps, c.count, ws.list, ws.nlist, ws.syn, nullptr, 0, c.pos8,
+                        nullptr, c.pos_stride, c.cnt, c.ok, c.corrected, g.num_cu, s));
+    STAGE(g, POPORON_AMD_KERNEL_APPLY, s,
+          nr ? rsk_apply_era_nr(&prm, ws.meta, ws.ext, c.data, c.ds, c.par, c.ps, c.count, npar, s)
+             : rsk_apply_era(&prm, ws.meta, ws.ext, c.data, c.ds, c.par, c.ps, c.count, s));
+    return ws_release(h, w, s);
+}
+
+/* ROUTE_ERA_RECORD: u32 slots and u8 slots in unaligned rows */
+static bool launch_era_record(poporon_t *h, const DecodeCall &c)
+{
+    GpuCtx &g = h->gpu;
+    hipStream_t s = c.s;
+    const RsCorrParams prm = corr_params(h, c.size);
+    DecodeWs w;
+    if (!ws_acquire(h, c.rem, c.rem_cap, c.count, s, w))
+        return false;
+    const RsSplitWs &ws = w.ws;
+    STAGE(g, POPORON_AMD_KERNEL_REMAINDER, s,
+          rsk_syndrome(g.tab, c.data, c.ds, c.par, c.ps, (uint32_t)c.size, c.count, ws.syn, g.num_cu, s));
+    STAGE(g, POPORON_AMD_KERNEL_CORRECT, s,
+          rsk_correct_era_rec(g.tab, &prm, c.count, ws.syn, c.pos8, c.pos32, c.pos_stride, c.cnt, c.ok, c.corrected,
+                              ws.ext, ws.meta, g.num_cu, s));
+    STAGE(g, POPORON_AMD_KERNEL_APPLY, s,
+          rsk_apply_era(&prm, ws.meta, ws.ext, c.data, c.ds, c.par, c.ps, c.count, s));
+    return ws_release(h, w, s);
+}
+
+/* ROUTE_CORRECT: syndromes, then the whole decode in one kernel */
+static bool launch_correct(poporon_t *h, const DecodeCall &c)
+{
+    GpuCtx &g = h->gpu;
+    hipStream_t s = c.s;
+    const RsCorrParams prm = corr_params(h, c.size);
+    DecodeWs w;
+    /* external syndromes and no caller workspace: none at all (rsk_correct reads c.ext_syn, never rem) */
+    if ((c.rem || !c.ext_syn) && !ws_acquire(h, c.rem, c.rem_cap, c.count, s, w))
+        return false;
+    if (!c.ext_syn)
+        STAGE(g, POPORON_AMD_KERNEL_REMAINDER, s,
+              rsk_syndrome(g.tab, c.data, c.ds, c.par, c.ps, (uint32_t)c.size, c.count, w.rem, g.num_cu, s));
+    STAGE(g, POPORON_AMD_KERNEL_CORRECT, s,
+          rsk_correct(g.tab, &prm, c.data, c.ds, c.par, c.ps, c.count, w.rem, c.ext_syn, c.ext_stride, c.pos8, c.pos32,
+                      c.pos_stride, c.cnt, c.ok, c.corrected, g.num_cu, s));
+    return ws_release(h, w, s);
+}
+
+/* One batch decode on the device: the route, then its launcher */
+static bool launch_decode(poporon_t *h, const DecodeCall &c)
+{
+    GpuCtx &g = h->gpu;
+    hipStream_t s = c.s;
+    /* rsk_decode1's mode: 0 errors, 1 erasure slots, 2 external syndromes */
+    const uint32_t mode1 = c.ext_syn ? 2u : (c.pos8 || c.pos32) ? 1u : 0u;
+    switch (decode_route(h, c)) {
+    case ROUTE_BCH:
+        if (c.ext_syn || c.pos8 || c.pos32)
+            return fail("BCH has no erasure or external-syndrome decode");
+        STAGE(g, POPORON_AMD_KERNEL_CORRECT, s,
+              bchk_decode(&h->bch, c.data, c.ds, c.par, c.ps, c.count, c.ok, c.corrected, g.num_cu, s));
+        return true;
+    case ROUTE_SINGLE: { /* (rs_single.hip; P.nr = num_roots; it always runs the check) */
+        const RsCorrParams prm = corr_params(h, c.size);
+        STAGE(g, POPORON_AMD_KERNEL_SINGLE, s,
+              rsk_decode1(g.tab, &prm, mode1, c.data, c.par, c.pos8, c.pos32, c.cnt, 1u, c.ext_syn, c.ok, c.corrected,
+                          nullptr, 0, s));
+        return true;
     }
-    KernelTimer t(h->gpu, POPORON_AMD_KERNEL_CORRECT, s);
-    HIP_OK(rsk_correct(h->gpu.tab, &prm, d_data, ds, d_par, ps, count, rem, ext_syn, ext_stride, pos8, pos32,
-                       pos_stride, cnt, ok, corrected, h->gpu.num_cu, s));
-    t.done();
-    return !shared || rem_release(h->gpu, s);
+    case ROUTE_GENERAL: {
+        const RsGenParams prm = gen_params(h, c.size);
+        STAGE(g, POPORON_AMD_KERNEL_CORRECT, s,
+              gen_wave(h, c.count, false, c.size)
+                  ? rsgw_decode(g.gtab, &prm, c.data, c.ds, c.par, c.ps, c.count, c.ext_syn, c.ext_stride, c.pos8,
+                                c.pos32, c.pos_stride, c.cnt, c.ok, c.corrected, nullptr, nullptr, nullptr, 0u,
+                                g.num_cu, s)
+                  : rsg_decode(g.gtab, &prm, c.data, c.ds, c.par, c.ps, c.count, c.ext_syn, c.ext_stride, c.pos8,
+                               c.pos32, c.pos_stride, c.cnt, c.ok, c.corrected, g.num_cu, s));
+        return true;
+    }
+    case ROUTE_WAVE: {
+        const RsCorrParams prm = corr_params(h, c.size);
+        STAGE(g, POPORON_AMD_KERNEL_WAVE, s,
+              rsk_wave(g.tab, &prm, c.data, c.ds, c.par, c.ps, c.count, nullptr, nullptr, nullptr, c.ext_syn,
+                       c.ext_stride, c.pos8, c.pos32, c.pos_stride, c.cnt, c.ok, c.corrected, g.num_cu, s));
+        return true;
+    }
+    case ROUTE_SPLIT:
+        return launch_split(h, c);
+    case ROUTE_ERRATA:
+        return launch_errata(h, c, false, true);
+    case ROUTE_ERA_ERRATA:
+        return launch_errata(h, c, true, true);
+    case ROUTE_ERA:
+        return launch_errata(h, c, true, false);
+    case ROUTE_ERA_RECORD:
+        return launch_era_record(h, c);
+    case ROUTE_CORRECT:
+        return launch_correct(h, c);
+    }
+    return false; /* (every route returns above) */
 }
 
 /* d_dirty[c] = codeword c's syndrome is nonzero (RS handles) */
@@ -2021,8 +2041,7 @@ static bool launch_check(poporon_t *h, const uint8_t *d_data, size_t data_stride
         HIP_OK(rsk_check_nr(h->gpu.tab, d_data, data_stride, d_parity, parity_stride, (uint32_t)size, count, d_dirty,
                             h->rs->num_roots, h->gpu.num_cu, s));
     } else {
-        RsGenParams prm = h->gen;
-        prm.size = (uint32_t)size;
+        const RsGenParams prm = gen_params(h, size);
         if (gen_wave(h, count, false, size))
             HIP_OK(rsgw_check(h->gpu.gtab, &prm, d_data, data_stride, d_parity, parity_stride, count, d_dirty,
                               nullptr, 0, h->gpu.num_cu, s));
@@ -2069,42 +2088,30 @@ EXPORT bool poporon_syndrome_batch_device(poporon_t *h, const uint8_t *d_data, s
     BatchScope bsc{h->gpu, (hipStream_t)stream, false};
     DeviceGuard dg(h->gpu.device);
     hipStream_t s = (hipStream_t)stream;
-    if (h->nrsplit) { /* fewer roots: the LFSR kernel's npar syndromes, then their logs */
-        if (!ensure_rem(h, count) || !rem_acquire(h->gpu, s))
-            return false;
-        {
-            KernelTimer t(h->gpu, POPORON_AMD_KERNEL_REMAINDER, s);
-            HIP_OK(rsk_syndrome_reset_nr(h->gpu.tab, d_data, data_stride, d_parity, parity_stride, (uint32_t)size,
-                                         count, h->gpu.rem, nullptr, h->rs->num_roots, h->gpu.num_cu, s));
-            t.done();
-        }
-        HIP_OK(rsk_syn_log_nr(h->gpu.tab, h->gpu.rem, count, d_syndromes, syndrome_stride, d_nonzero,
-                              h->rs->num_roots, s));
-        return rem_release(h->gpu, s);
-    }
-    if (!h->fast) {
-        RsGenParams prm = h->gen;
-        prm.size = (uint32_t)size;
-        KernelTimer t(h->gpu, POPORON_AMD_KERNEL_REMAINDER, s);
-        if (gen_wave(h, count, false, size))
-            HIP_OK(rsgw_check(h->gpu.gtab, &prm, d_data, data_stride, d_parity, parity_stride, count, d_nonzero,
-                              d_syndromes, syndrome_stride, h->gpu.num_cu, s));
-        else
-            HIP_OK(rsg_check(h->gpu.gtab, &prm, d_data, data_stride, d_parity, parity_stride, count, d_nonzero,
-                             d_syndromes, syndrome_stride, h->gpu.num_cu, s));
-        t.done();
+    GpuCtx &g = h->gpu;
+    const uint32_t nr = h->rs->num_roots;
+    if (!h->fast && !h->nrsplit) {
+        const RsGenParams prm = gen_params(h, size);
+        STAGE(g, POPORON_AMD_KERNEL_REMAINDER, s,
+              gen_wave(h, count, false, size)
+                  ? rsgw_check(g.gtab, &prm, d_data, data_stride, d_parity, parity_stride, count, d_nonzero,
+                               d_syndromes, syndrome_stride, g.num_cu, s)
+                  : rsg_check(g.gtab, &prm, d_data, data_stride, d_parity, parity_stride, count, d_nonzero, d_syndromes,
+                              syndrome_stride, g.num_cu, s));
         return true;
     }
-    if (!ensure_rem(h, count) || !rem_acquire(h->gpu, s))
+    /* the LFSR kernel's syndromes into the handle's workspace (fewer roots: npar of them), then their logs */
+    DecodeWs w;
+    if (!ws_acquire(h, nullptr, 0, count, s, w))
         return false;
-    {
-        KernelTimer t(h->gpu, POPORON_AMD_KERNEL_REMAINDER, s);
-        HIP_OK(rsk_syndrome(h->gpu.tab, d_data, data_stride, d_parity, parity_stride, (uint32_t)size, count,
-                            h->gpu.rem, h->gpu.num_cu, s));
-        t.done();
-    }
-    HIP_OK(rsk_syn_log(h->gpu.tab, h->gpu.rem, count, d_syndromes, syndrome_stride, d_nonzero, s));
-    return rem_release(h->gpu, s);
+    STAGE(g, POPORON_AMD_KERNEL_REMAINDER, s,
+          h->nrsplit ? rsk_syndrome_reset_nr(g.tab, d_data, data_stride, d_parity, parity_stride, (uint32_t)size, count,
+                                             w.rem, nullptr, nr, g.num_cu, s)
+                     : rsk_syndrome(g.tab, d_data, data_stride, d_parity, parity_stride, (uint32_t)size, count, w.rem,
+                                    g.num_cu, s));
+    HIP_OK(h->nrsplit ? rsk_syn_log_nr(g.tab, w.rem, count, d_syndromes, syndrome_stride, d_nonzero, nr, s)
+                      : rsk_syn_log(g.tab, w.rem, count, d_syndromes, syndrome_stride, d_nonzero, s));
+    return ws_release(h, w, s);
 }
 
 EXPORT bool poporon_encode_batch_device(poporon_t *h, const uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
@@ -2128,20 +2135,16 @@ EXPORT bool poporon_decode_batch_device(poporon_t *h, uint8_t *d_data, size_t da
                                         size_t positions_stride, const uint8_t *d_counts, uint8_t *d_ok,
                                         uint8_t *d_corrected, void *stream)
 {
-    if (!h || (count && (!d_data || !d_parity || !d_ok)))
-        return fail("NULL argument");
-    if (is_ldpc(h, "poporon_decode_batch_device"))
+    if (!decode_row_args(h, "poporon_decode_batch_device", false, d_data, d_parity, size, count, d_positions,
+                         positions_stride, d_counts, d_ok))
         return false;
-    if (d_positions && (h->fec_type != PPLN_FEC_RS || !d_counts || positions_stride < h->rs->num_roots))
-        return fail("erasure batch needs an RS handle, counts and positions_stride >= num_roots");
-    if (!check_decode_size(h, size))
-        return fail("decode size %zu outside [1, %u]", size, (unsigned)kmax(h));
     if (!batch_enter(h))
         return false;
     BatchScope bsc{h->gpu, (hipStream_t)stream, false};
     DeviceGuard dg(h->gpu.device);
-    return launch_decode(h, d_data, data_stride, d_parity, parity_stride, size, count, nullptr, 0, d_positions,
-                         nullptr, positions_stride, d_counts, d_ok, d_corrected, (hipStream_t)stream);
+    return launch_decode(h, {.data = d_data, .ds = data_stride, .par = d_parity, .ps = parity_stride, .size = size,
+                             .count = count, .pos8 = d_positions, .pos_stride = positions_stride, .cnt = d_counts,
+                             .ok = d_ok, .corrected = d_corrected, .s = (hipStream_t)stream});
 }
 
 EXPORT bool poporon_decode_batch_syndrome_device(poporon_t *h, uint8_t *d_data, size_t data_stride,
@@ -2161,8 +2164,9 @@ EXPORT bool poporon_decode_batch_syndrome_device(poporon_t *h, uint8_t *d_data, 
         return false;
     BatchScope bsc{h->gpu, (hipStream_t)stream, false};
     DeviceGuard dg(h->gpu.device);
-    return launch_decode(h, d_data, data_stride, d_parity, parity_stride, size, count, d_syndromes, syndrome_stride,
-                         nullptr, nullptr, 0, nullptr, d_ok, d_corrected, (hipStream_t)stream);
+    return launch_decode(h, {.data = d_data, .ds = data_stride, .par = d_parity, .ps = parity_stride, .size = size,
+                             .count = count, .ext_syn = d_syndromes, .ext_stride = syndrome_stride, .ok = d_ok,
+                             .corrected = d_corrected, .s = (hipStream_t)stream});
 }
 
 /* ------------------------------------------------------------------------ */
@@ -2230,15 +2234,58 @@ static bool pipe_slot(poporon_t *h, GpuCtx::PipeSlot &ps, size_t bytes)
     return true;
 }
 
-/* wait for every slot (after an error: nothing may still be in flight into
- * the pinned buffers) */
-static void pipe_drain(GpuCtx &g)
+/*
+ * The one loop of every host-memory batch: `count` rows in chunks of `chunk`
+ * through `nslots` slots of at least slot_bytes each.  Chunk i goes to slot
+ * i % nslots: in(host, c0, n) packs rows [c0, c0 + n) into the slot's pinned
+ * buffer, run(slot, n) copies in, launches and copies back on the slot's
+ * stream, and out(host, c0, n) hands the results to the caller's arrays once
+ * the slot's event has fired -- when the slot is needed again, or oldest first
+ * after the last chunk.  One slot: a synchronous loop.  After a failure every
+ * slot's stream is synchronised before the call returns (nothing may still be
+ * in flight into the pinned buffers) and the error text saved by whatever
+ * failed is raised again, `what` if nothing saved one.
+ */
+template <typename In, typename Run, typename Out>
+static bool host_chunks(poporon_t *h, GpuCtx::PipeSlot *slots, size_t nslots, size_t count, size_t chunk,
+                        size_t slot_bytes, In in, Run run, Out out, const char *what)
 {
-    for (auto &ps : g.pipe) {
-        if (ps.stream)
-            (void)hipStreamSynchronize(ps.stream);
+    for (size_t k = 0; k < nslots; k++)
+        if (!pipe_slot(h, slots[k], slot_bytes))
+            return false;
+    auto finish = [&](GpuCtx::PipeSlot &ps) -> bool {
+        if (!ps.busy)
+            return true;
         ps.busy = false;
+        HIP_OK(hipEventSynchronize(ps.done));
+        out(ps.host, ps.c0, ps.n);
+        return true;
+    };
+    bool good = true;
+    size_t i = 0;
+    for (size_t c0 = 0; good && c0 < count; c0 += chunk, i++) {
+        GpuCtx::PipeSlot &ps = slots[i % nslots];
+        if (!(good = finish(ps)))
+            break;
+        const size_t n = std::min(chunk, count - c0);
+        in(ps.host, c0, n);
+        good = run(ps, n) && hipEventRecord(ps.done, ps.stream) == hipSuccess;
+        ps.busy = true;
+        ps.c0 = c0;
+        ps.n = n;
     }
+    for (size_t k = 0; good && k < nslots; k++) /* oldest first */
+        good = finish(slots[(i + k) % nslots]);
+    if (!good) {
+        const std::string msg = g_last_error.empty() ? std::string(what) : g_last_error;
+        for (size_t k = 0; k < nslots; k++) {
+            if (slots[k].stream)
+                (void)hipStreamSynchronize(slots[k].stream);
+            slots[k].busy = false;
+        }
+        return fail("%s", msg.c_str());
+    }
+    return true;
 }
 
 EXPORT bool poporon_encode_batch(poporon_t *h, const uint8_t *data, size_t data_stride, uint8_t *parity,
@@ -2254,136 +2301,88 @@ EXPORT bool poporon_encode_batch(poporon_t *h, const uint8_t *data, size_t data_
         return false;
     BatchScope bsc{h->gpu, nullptr, true};
     DeviceGuard dg(h->gpu.device);
-    GpuCtx &g = h->gpu;
     const size_t nr = par_bytes(h);
     const size_t chunk = std::max<size_t>(1, std::min(count, kPipeChunk));
-    for (auto &ps : g.pipe)
-        if (!pipe_slot(h, ps, chunk * (size + nr) + 64))
-            return false;
-    /* parity of the slot's chunk -> caller */
-    auto finish = [&](GpuCtx::PipeSlot &ps) -> bool {
-        if (!ps.busy)
+    /* slot layout for n rows: [data size n | parity nr n] */
+    return host_chunks(
+        h, h->gpu.pipe, PIPE_SLOTS, count, chunk, chunk * (size + nr) + 64,
+        [&](uint8_t *hb, size_t c0, size_t n) { copy_rows(hb, size, data + c0 * data_stride, data_stride, size, n); },
+        [&](GpuCtx::PipeSlot &ps, size_t n) {
+            uint8_t *dp = ps.dev + n * size;
+            HIP_OK(hipMemcpyAsync(ps.dev, ps.host, n * size, hipMemcpyHostToDevice, ps.stream));
+            if (!launch_encode(h, ps.dev, size, dp, nr, size, n, ps.stream))
+                return false;
+            HIP_OK(hipMemcpyAsync(ps.host + n * size, dp, n * nr, hipMemcpyDeviceToHost, ps.stream));
             return true;
-        ps.busy = false;
-        HIP_OK(hipEventSynchronize(ps.done));
-        copy_rows(parity + ps.c0 * parity_stride, parity_stride, ps.host + ps.n * size, nr, nr, ps.n);
-        return true;
-    };
-    bool ok = true;
-    size_t i = 0;
-    for (size_t c0 = 0; ok && c0 < count; c0 += chunk, i++) {
-        GpuCtx::PipeSlot &ps = g.pipe[i % PIPE_SLOTS];
-        if (!(ok = finish(ps)))
-            break;
-        const size_t n = std::min(chunk, count - c0);
-        uint8_t *hd = ps.host, *dd = ps.dev, *dp = ps.dev + n * size;
-        copy_rows(hd, size, data + c0 * data_stride, data_stride, size, n);
-        ok = hipMemcpyAsync(dd, hd, n * size, hipMemcpyHostToDevice, ps.stream) == hipSuccess &&
-             launch_encode(h, dd, size, dp, nr, size, n, ps.stream) &&
-             hipMemcpyAsync(hd + n * size, dp, n * nr, hipMemcpyDeviceToHost, ps.stream) == hipSuccess &&
-             hipEventRecord(ps.done, ps.stream) == hipSuccess;
-        ps.busy = true;
-        ps.c0 = c0;
-        ps.n = n;
-    }
-    for (size_t k = 0; ok && k < PIPE_SLOTS; k++) /* oldest first */
-        ok = finish(g.pipe[(i + k) % PIPE_SLOTS]);
-    if (!ok) {
-        const std::string msg = g_last_error.empty() ? std::string("HIP failure in the host pipeline") : g_last_error;
-        pipe_drain(g);
-        return fail("%s", msg.c_str());
-    }
-    return true;
+        },
+        [&](const uint8_t *hb, size_t c0, size_t n) {
+            copy_rows(parity + c0 * parity_stride, parity_stride, hb + n * size, nr, nr, n);
+        },
+        "HIP failure in the host pipeline");
 }
 
 EXPORT bool poporon_decode_batch(poporon_t *h, uint8_t *data, size_t data_stride, uint8_t *parity,
                                  size_t parity_stride, size_t size, size_t count, const uint8_t *positions,
                                  size_t positions_stride, const uint8_t *counts, uint8_t *ok, uint8_t *corrected)
 {
-    if (!h || (count && (!data || !parity || !ok)))
-        return fail("NULL argument");
-    if (is_ldpc(h, "poporon_decode_batch"))
+    if (!decode_row_args(h, "poporon_decode_batch", false, data, parity, size, count, positions, positions_stride,
+                         counts, ok))
         return false;
-    if (positions && (h->fec_type != PPLN_FEC_RS || !counts || positions_stride < h->rs->num_roots))
-        return fail("erasure batch needs an RS handle, counts and positions_stride >= num_roots");
-    if (!check_decode_size(h, size))
-        return fail("decode size %zu outside [1, %u]", size, (unsigned)kmax(h));
     if (!batch_enter(h))
         return false;
     BatchScope bsc{h->gpu, nullptr, true};
     DeviceGuard dg(h->gpu.device);
-    GpuCtx &g = h->gpu;
     const size_t nr = par_bytes(h);
     const size_t w = size + nr;
     const size_t chunk = std::max<size_t>(1, std::min(count, kPipeChunk));
-    /* slot layout: [codewords w*n | ok n | cor n | positions nr*n | counts n | decode workspace (device)] */
     const size_t per = w + 2 + (positions ? nr + 1 : 0);
-    /* parity right after the data in rows of equal stride: move whole rows */
+    /* parity right after the data in rows of equal stride (the wire layout): move whole rows */
     const bool rows = parity == data + size && parity_stride == data_stride;
-    for (auto &ps : g.pipe)
-        if (!pipe_slot(h, ps, chunk * per + 512 + rs_ws_bytes(chunk)))
-            return false;
-    auto finish = [&](GpuCtx::PipeSlot &ps) -> bool {
-        if (!ps.busy)
+    /* slot layout for n rows: [codewords w n | ok n | cor n | to 16 | positions nr n | counts n | to 256 |
+     * decode workspace (device)]; positions 16-byte aligned: the 32-erasure kernel reads them as uint4 */
+    auto o_ok = [&](size_t n) { return n * w; };
+    auto o_pos = [&](size_t n) { return rs_ws_round16(n * w + 2 * n); };
+    auto o_cnt = [&](size_t n) { return o_pos(n) + (positions ? n * nr : 0); };
+    auto o_rem = [&](size_t n) { return (o_cnt(n) + (positions ? n : 0) + 255) & ~(size_t)255; };
+    return host_chunks(
+        h, h->gpu.pipe, PIPE_SLOTS, count, chunk, chunk * per + 512 + rs_ws_bytes(chunk),
+        [&](uint8_t *hb, size_t c0, size_t n) {
+            if (rows) {
+                copy_rows(hb, w, data + c0 * data_stride, data_stride, w, n);
+            } else {
+                copy_rows(hb, w, data + c0 * data_stride, data_stride, size, n);
+                copy_rows(hb + size, w, parity + c0 * parity_stride, parity_stride, nr, n);
+            }
+            if (positions) {
+                copy_rows(hb + o_pos(n), nr, positions + c0 * positions_stride, positions_stride, nr, n);
+                memcpy(hb + o_cnt(n), counts + c0, n);
+            }
+        },
+        [&](GpuCtx::PipeSlot &ps, size_t n) {
+            uint8_t *dc = ps.dev;
+            HIP_OK(hipMemcpyAsync(dc, ps.host, n * w, hipMemcpyHostToDevice, ps.stream));
+            if (positions)
+                HIP_OK(hipMemcpyAsync(dc + o_pos(n), ps.host + o_pos(n), n * nr + n, hipMemcpyHostToDevice, ps.stream));
+            if (!launch_decode(h, {.data = dc, .ds = w, .par = dc + size, .ps = w, .size = size, .count = n,
+                                   .pos8 = positions ? dc + o_pos(n) : nullptr, .pos_stride = nr,
+                                   .cnt = positions ? dc + o_cnt(n) : nullptr, .ok = dc + o_ok(n),
+                                   .corrected = dc + o_ok(n) + n, .s = ps.stream, .rem = dc + o_rem(n), .rem_cap = n}))
+                return false;
+            HIP_OK(hipMemcpyAsync(ps.host, dc, n * w + 2 * n, hipMemcpyDeviceToHost, ps.stream));
             return true;
-        ps.busy = false;
-        HIP_OK(hipEventSynchronize(ps.done));
-        const size_t n = ps.n;
-        if (rows) { /* wire layout: whole codeword rows */
-            copy_rows(data + ps.c0 * data_stride, data_stride, ps.host, w, w, n);
-        } else {
-            copy_rows(data + ps.c0 * data_stride, data_stride, ps.host, w, size, n);
-            copy_rows(parity + ps.c0 * parity_stride, parity_stride, ps.host + size, w, nr, n);
-        }
-        memcpy(ok + ps.c0, ps.host + n * w, n);
-        if (corrected)
-            memcpy(corrected + ps.c0, ps.host + n * w + n, n);
-        return true;
-    };
-    bool good = true;
-    size_t i = 0;
-    for (size_t c0 = 0; good && c0 < count; c0 += chunk, i++) {
-        GpuCtx::PipeSlot &ps = g.pipe[i % PIPE_SLOTS];
-        if (!(good = finish(ps)))
-            break;
-        const size_t n = std::min(chunk, count - c0);
-        uint8_t *hc = ps.host, *dc = ps.dev;
-        /* positions 16-byte aligned: the 32-erasure kernel reads them as uint4 */
-        const size_t o_ok = n * w, o_cor = o_ok + n, o_pos = (o_cor + n + 15) & ~(size_t)15,
-                     o_cnt = o_pos + (positions ? n * nr : 0);
-        const size_t o_rem = (o_cnt + (positions ? n : 0) + 255) & ~(size_t)255;
-        /* codeword rows [data | parity] */
-        if (rows) {
-            copy_rows(hc, w, data + c0 * data_stride, data_stride, w, n);
-        } else {
-            copy_rows(hc, w, data + c0 * data_stride, data_stride, size, n);
-            copy_rows(hc + size, w, parity + c0 * parity_stride, parity_stride, nr, n);
-        }
-        size_t in_bytes = n * w;
-        if (positions) {
-            copy_rows(hc + o_pos, nr, positions + c0 * positions_stride, positions_stride, nr, n);
-            memcpy(hc + o_cnt, counts + c0, n);
-        }
-        good = hipMemcpyAsync(dc, hc, in_bytes, hipMemcpyHostToDevice, ps.stream) == hipSuccess &&
-               (!positions || hipMemcpyAsync(dc + o_pos, hc + o_pos, n * nr + n, hipMemcpyHostToDevice,
-                                             ps.stream) == hipSuccess) &&
-               launch_decode(h, dc, w, dc + size, w, size, n, nullptr, 0, positions ? dc + o_pos : nullptr, nullptr,
-                             nr, positions ? dc + o_cnt : nullptr, dc + o_ok, dc + o_cor, ps.stream, dc + o_rem,
-                             n) &&
-               hipMemcpyAsync(hc, dc, n * w + 2 * n, hipMemcpyDeviceToHost, ps.stream) == hipSuccess &&
-               hipEventRecord(ps.done, ps.stream) == hipSuccess;
-        ps.busy = true;
-        ps.c0 = c0;
-        ps.n = n;
-    }
-    for (size_t k = 0; good && k < PIPE_SLOTS; k++)
-        good = finish(g.pipe[(i + k) % PIPE_SLOTS]);
-    if (!good) {
-        const std::string msg = g_last_error.empty() ? std::string("HIP failure in the host pipeline") : g_last_error;
-        pipe_drain(g);
-        return fail("%s", msg.c_str());
-    }
-    return true;
+        },
+        [&](const uint8_t *hb, size_t c0, size_t n) {
+            if (rows) {
+                copy_rows(data + c0 * data_stride, data_stride, hb, w, w, n);
+            } else {
+                copy_rows(data + c0 * data_stride, data_stride, hb, w, size, n);
+                copy_rows(parity + c0 * parity_stride, parity_stride, hb + size, w, nr, n);
+            }
+            memcpy(ok + c0, hb + o_ok(n), n);
+            if (corrected)
+                memcpy(corrected + c0, hb + o_ok(n) + n, n);
+        },
+        "HIP failure in the host pipeline");
 }
 
 /* ------------------------------------------------------------------------ */
@@ -2512,23 +2511,9 @@ static const size_t kLdpcChunkBytes = (size_t)8 << 20;
 template <typename In, typename Run, typename Out>
 static bool ldpc_host_chunks(poporon_t *h, size_t count, size_t row_bytes, In in, Run run, Out out)
 {
-    GpuCtx::PipeSlot &ps = h->gpu.pipe[0];
     const size_t chunk = std::max<size_t>(1, std::min(count, kLdpcChunkBytes / row_bytes));
-    if (!pipe_slot(h, ps, chunk * row_bytes + 64))
-        return false;
-    for (size_t c0 = 0; c0 < count; c0 += chunk) {
-        const size_t n = std::min(chunk, count - c0);
-        in(ps.host, c0, n);
-        const bool good = run(ps, n) && hipStreamSynchronize(ps.stream) == hipSuccess;
-        if (!good) {
-            const std::string msg =
-                g_last_error.empty() ? std::string("HIP failure in an LDPC host batch") : g_last_error;
-            (void)hipStreamSynchronize(ps.stream);
-            return fail("%s", msg.c_str());
-        }
-        out(ps.host, c0, n);
-    }
-    return true;
+    return host_chunks(h, &h->gpu.pipe[0], 1, count, chunk, chunk * row_bytes + 64, in, run, out,
+                       "HIP failure in an LDPC host batch");
 }
 
 EXPORT bool poporon_ldpc_encode_batch(poporon_t *h, uint8_t *data, size_t data_stride, uint8_t *parity,
@@ -2706,12 +2691,13 @@ struct RepOut {
  * behind the message, both strides size + nr) are one device copy, stamped
  * with the timer's events by hand since no kernel of ours runs; any other
  * placement is gathered by rs_snapshot_k. */
-static bool rep_snapshot(poporon_t *h, const uint8_t *d, size_t ds, const uint8_t *p, size_t ps, size_t size, size_t n,
-                         hipStream_t s)
+static bool rep_snapshot(poporon_t *h, const DecodeCall &c)
 {
     GpuCtx &g = h->gpu;
     const uint32_t nr = h->rs->num_roots;
-    const size_t w = size + nr;
+    const uint8_t *d = c.data, *p = c.par;
+    const size_t ds = c.ds, ps = c.ps, size = c.size, n = c.count, w = size + nr;
+    hipStream_t s = c.s;
     KernelTimer t(g, POPORON_AMD_KERNEL_SNAPSHOT, s);
     if (p == d + size && ds == w && ps == w) {
         if (t.a)
@@ -2729,13 +2715,11 @@ static bool rep_snapshot(poporon_t *h, const uint8_t *d, size_t ds, const uint8_
 }
 
 /* the n rows as they are now against the snapshot buffer */
-static bool rep_diff(poporon_t *h, const uint8_t *d, size_t ds, const uint8_t *p, size_t ps, size_t size, size_t n,
-                     const RepOut &o, size_t c0, hipStream_t s)
+static bool rep_diff(poporon_t *h, const DecodeCall &c, const RepOut &o, size_t c0)
 {
-    KernelTimer t(h->gpu, POPORON_AMD_KERNEL_REPORT, s);
-    HIP_OK(rsk_report(d, ds, p, ps, h->gpu.rep, (uint32_t)size, h->rs->num_roots, n, o.num + c0,
-                      o.pos + c0 * o.stride, o.val + c0 * o.stride, o.stride, s));
-    t.done();
+    STAGE(h->gpu, POPORON_AMD_KERNEL_REPORT, c.s,
+          rsk_report(c.data, c.ds, c.par, c.ps, h->gpu.rep, (uint32_t)c.size, h->rs->num_roots, c.count, o.num + c0,
+                     o.pos + c0 * o.stride, o.val + c0 * o.stride, o.stride, c.s));
     return true;
 }
 
@@ -2780,9 +2764,7 @@ static bool ilv_args(const poporon_t *h, const char *what, const IlvCall &c)
     return true;
 }
 
-static bool rep_run(poporon_t *h, uint8_t *d, size_t ds, uint8_t *p, size_t ps, size_t size, size_t count,
-                    const uint8_t *pos, size_t pos_stride, const uint8_t *cnt, uint8_t *ok, uint8_t *cor,
-                    const RepOut &o, hipStream_t s);
+static bool rep_run(poporon_t *h, const DecodeCall &c, const RepOut &o);
 
 /* device pointers; the caller holds the batch scope and the device */
 static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
@@ -2793,8 +2775,10 @@ static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
     const bool staged = c.depth > 1;
     const bool report = c.op == ILV_DECODE && c.rep.num;
     if (report && !staged) /* depth 1 is the row layout: the row report */
-        return rep_run(h, c.data, c.ds, c.par, c.ps, c.size, c.count, c.pos, c.pos_stride, c.cnt, c.ok, c.cor, c.rep,
-                       s);
+        return rep_run(h, {.data = c.data, .ds = c.ds, .par = c.par, .ps = c.ps, .size = c.size, .count = c.count,
+                           .pos8 = c.pos, .pos_stride = c.pos_stride, .cnt = c.cnt, .ok = c.ok, .corrected = c.cor,
+                           .s = s},
+                       c.rep);
     if (report && !ensure_rep(h, std::min(c.count, cf) * c.depth))
         return false;
     if (staged && (!ensure_ilv(h, std::min(c.count, cf) * c.depth) || !rem_acquire(g, s)))
@@ -2804,34 +2788,32 @@ static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
         uint8_t *fd = c.data + f0 * c.ds, *fp = c.par + f0 * c.ps;
         uint8_t *rd = staged ? g.ilv : fd, *rp = staged ? g.ilv + c.size : fp;
         const size_t rds = staged ? c.size + nr : c.ds, rps = staged ? c.size + nr : c.ps; /* staged: wire rows */
-        if (staged) {
-            KernelTimer t(g, POPORON_AMD_KERNEL_ILV_GATHER, s);
-            HIP_OK(rsk_ilv_gather(fd, c.ds, fp, c.ps, g.ilv, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
-                                  c.op != ILV_ENCODE, s));
-            t.done();
-        }
+        if (staged)
+            STAGE(g, POPORON_AMD_KERNEL_ILV_GATHER, s,
+                  rsk_ilv_gather(fd, c.ds, fp, c.ps, g.ilv, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
+                                 c.op != ILV_ENCODE, s));
         if (c.op == ILV_ENCODE) {
             if (!launch_encode(h, rd, rds, rp, rps, c.size, ncw, s))
                 return false;
         } else if (c.op == ILV_DECODE) {
-            const uint8_t *pos = c.pos ? c.pos + c0 * c.pos_stride : nullptr;
+            const DecodeCall d = {.data = rd, .ds = rds, .par = rp, .ps = rps, .size = c.size, .count = ncw,
+                                  .pos8 = c.pos ? c.pos + c0 * c.pos_stride : nullptr, .pos_stride = c.pos_stride,
+                                  .cnt = c.pos ? c.cnt + c0 : nullptr, .ok = c.ok + c0,
+                                  .corrected = c.cor ? c.cor + c0 : nullptr, .s = s};
             /* report: the staging rows as gathered are the snapshot (wire rows: one device copy) */
-            if (report && !rep_snapshot(h, rd, rds, rp, rps, c.size, ncw, s))
+            if (report && !rep_snapshot(h, d))
                 return false;
-            if (!launch_decode(h, rd, rds, rp, rps, c.size, ncw, nullptr, 0, pos, nullptr, c.pos_stride,
-                               pos ? c.cnt + c0 : nullptr, c.ok + c0, c.cor ? c.cor + c0 : nullptr, s))
+            if (!launch_decode(h, d))
                 return false;
-            if (report && !rep_diff(h, rd, rds, rp, rps, c.size, ncw, c.rep, c0, s))
+            if (report && !rep_diff(h, d, c.rep, c0))
                 return false;
         } else if (!launch_check(h, rd, rds, rp, rps, c.size, ncw, c.dirty + c0, s)) {
             return false;
         }
-        if (staged && c.op != ILV_CHECK) {
-            KernelTimer t(g, POPORON_AMD_KERNEL_ILV_SCATTER, s);
-            HIP_OK(rsk_ilv_scatter(g.ilv, fd, c.ds, fp, c.ps, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
-                                   c.op == ILV_DECODE, s));
-            t.done();
-        }
+        if (staged && c.op != ILV_CHECK)
+            STAGE(g, POPORON_AMD_KERNEL_ILV_SCATTER, s,
+                  rsk_ilv_scatter(g.ilv, fd, c.ds, fp, c.ps, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
+                                  c.op == ILV_DECODE, s));
     }
     return !staged || rem_release(g, s);
 }
@@ -2914,46 +2896,43 @@ static bool ilv_host(poporon_t *h, const char *what, const IlvCall &c)
     auto o_cnt = [&](size_t n) { return o_pos(n) + n * c.depth * eb; };
     auto o_ok = [&](size_t n) { return o_cnt(n) + n * c.depth; };
     auto o_cor = [&](size_t n) { return o_ok(n) + n * c.depth; };
-    GpuCtx::PipeSlot &ps = h->gpu.pipe[0];
-    if (!pipe_slot(h, ps, o_cor(chunk) + chunk * c.depth))
-        return false;
-    for (size_t f0 = 0; f0 < c.count; f0 += chunk) {
-        const size_t n = std::min(chunk, c.count - f0), ncw = n * c.depth, c0 = f0 * c.depth;
-        copy_rows(ps.host, fb, c.data + f0 * c.ds, c.ds, db, n);
-        if (c.op != ILV_ENCODE)
-            copy_rows(ps.host + db, fb, c.par + f0 * c.ps, c.ps, pb, n);
-        if (c.pos) {
-            copy_rows(ps.host + o_pos(n), nr, c.pos + c0 * c.pos_stride, c.pos_stride, nr, ncw);
-            memcpy(ps.host + o_cnt(n), c.cnt + c0, ncw);
-        }
-        const IlvCall d = {c.op,  ps.dev,
-                           fb,    ps.dev + db,
-                           fb,    c.size,
-                           c.depth, n,
-                           c.pos ? ps.dev + o_pos(n) : nullptr, nr,
-                           ps.dev + o_cnt(n), ps.dev + o_ok(n),
-                           ps.dev + o_cor(n), nullptr};
-        bool good = hipMemcpyAsync(ps.dev, ps.host, o_ok(n), hipMemcpyHostToDevice, ps.stream) == hipSuccess &&
-                    ilv_run(h, d, ps.stream) &&
-                    hipMemcpyAsync(ps.host, ps.dev, n * fb, hipMemcpyDeviceToHost, ps.stream) == hipSuccess;
-        if (good && c.op == ILV_DECODE)
-            good = hipMemcpyAsync(ps.host + o_ok(n), ps.dev + o_ok(n), 2 * ncw, hipMemcpyDeviceToHost, ps.stream) ==
-                   hipSuccess;
-        if (!good || hipStreamSynchronize(ps.stream) != hipSuccess) {
-            const std::string msg =
-                g_last_error.empty() ? std::string("HIP failure in an interleaved host batch") : g_last_error;
-            (void)hipStreamSynchronize(ps.stream);
-            return fail("%s", msg.c_str());
-        }
-        copy_rows(c.par + f0 * c.ps, c.ps, ps.host + db, fb, pb, n);
-        if (c.op == ILV_DECODE) {
-            copy_rows(c.data + f0 * c.ds, c.ds, ps.host, fb, db, n);
-            memcpy(c.ok + c0, ps.host + o_ok(n), ncw);
-            if (c.cor)
-                memcpy(c.cor + c0, ps.host + o_cor(n), ncw);
-        }
-    }
-    return true;
+    return host_chunks(
+        h, &h->gpu.pipe[0], 1, c.count, chunk, o_cor(chunk) + chunk * c.depth,
+        [&](uint8_t *hb, size_t f0, size_t n) {
+            const size_t ncw = n * c.depth, c0 = f0 * c.depth;
+            copy_rows(hb, fb, c.data + f0 * c.ds, c.ds, db, n);
+            if (c.op != ILV_ENCODE)
+                copy_rows(hb + db, fb, c.par + f0 * c.ps, c.ps, pb, n);
+            if (c.pos) {
+                copy_rows(hb + o_pos(n), nr, c.pos + c0 * c.pos_stride, c.pos_stride, nr, ncw);
+                memcpy(hb + o_cnt(n), c.cnt + c0, ncw);
+            }
+        },
+        [&](GpuCtx::PipeSlot &ps, size_t n) {
+            const IlvCall d = {.op = c.op, .data = ps.dev, .ds = fb, .par = ps.dev + db, .ps = fb, .size = c.size,
+                               .depth = c.depth, .count = n, .pos = c.pos ? ps.dev + o_pos(n) : nullptr,
+                               .pos_stride = nr, .cnt = ps.dev + o_cnt(n), .ok = ps.dev + o_ok(n),
+                               .cor = ps.dev + o_cor(n)};
+            HIP_OK(hipMemcpyAsync(ps.dev, ps.host, o_ok(n), hipMemcpyHostToDevice, ps.stream));
+            if (!ilv_run(h, d, ps.stream))
+                return false;
+            HIP_OK(hipMemcpyAsync(ps.host, ps.dev, n * fb, hipMemcpyDeviceToHost, ps.stream));
+            if (c.op == ILV_DECODE)
+                HIP_OK(hipMemcpyAsync(ps.host + o_ok(n), ps.dev + o_ok(n), 2 * n * c.depth, hipMemcpyDeviceToHost,
+                                      ps.stream));
+            return true;
+        },
+        [&](const uint8_t *hb, size_t f0, size_t n) {
+            const size_t ncw = n * c.depth, c0 = f0 * c.depth;
+            copy_rows(c.par + f0 * c.ps, c.ps, hb + db, fb, pb, n);
+            if (c.op == ILV_DECODE) {
+                copy_rows(c.data + f0 * c.ds, c.ds, hb, fb, db, n);
+                memcpy(c.ok + c0, hb + o_ok(n), ncw);
+                if (c.cor)
+                    memcpy(c.cor + c0, hb + o_cor(n), ncw);
+            }
+        },
+        "HIP failure in an interleaved host batch");
 }
 
 EXPORT bool poporon_encode_interleaved(poporon_t *h, const uint8_t *data, size_t data_stride, uint8_t *parity,
@@ -2987,26 +2966,25 @@ EXPORT bool poporon_decode_interleaved(poporon_t *h, uint8_t *data, size_t data_
  * for every decode route.  Device pointers; the caller holds the batch scope
  * and the device.
  */
-static bool rep_run(poporon_t *h, uint8_t *d, size_t ds, uint8_t *p, size_t ps, size_t size, size_t count,
-                    const uint8_t *pos, size_t pos_stride, const uint8_t *cnt, uint8_t *ok, uint8_t *cor,
-                    const RepOut &o, hipStream_t s)
+static bool rep_run(poporon_t *h, const DecodeCall &c, const RepOut &o)
 {
     GpuCtx &g = h->gpu;
     const size_t chunk = h->rep_chunk;
-    if (!ensure_rep(h, std::min(count, chunk)) || !rem_acquire(g, s))
+    if (!ensure_rep(h, std::min(c.count, chunk)) || !rem_acquire(g, c.s))
         return false;
-    for (size_t c0 = 0; c0 < count; c0 += chunk) {
-        const size_t n = std::min(chunk, count - c0);
-        uint8_t *cd = d + c0 * ds, *cp = p + c0 * ps;
-        if (!rep_snapshot(h, cd, ds, cp, ps, size, n, s))
-            return false;
-        if (!launch_decode(h, cd, ds, cp, ps, size, n, nullptr, 0, pos ? pos + c0 * pos_stride : nullptr, nullptr,
-                           pos_stride, pos ? cnt + c0 : nullptr, ok + c0, cor ? cor + c0 : nullptr, s))
-            return false;
-        if (!rep_diff(h, cd, ds, cp, ps, size, n, o, c0, s))
+    for (size_t c0 = 0; c0 < c.count; c0 += chunk) {
+        DecodeCall d = c; /* rows [c0, c0 + chunk) */
+        d.count = std::min(chunk, c.count - c0);
+        d.data += c0 * c.ds;
+        d.par += c0 * c.ps;
+        d.pos8 = c.pos8 ? c.pos8 + c0 * c.pos_stride : nullptr;
+        d.cnt = c.pos8 ? c.cnt + c0 : nullptr;
+        d.ok += c0;
+        d.corrected = c.corrected ? c.corrected + c0 : nullptr;
+        if (!rep_snapshot(h, d) || !launch_decode(h, d) || !rep_diff(h, d, o, c0))
             return false;
     }
-    return rem_release(g, s);
+    return rem_release(g, c.s);
 }
 
 /* what every report entry point checks about the report arrays */
@@ -3019,24 +2997,6 @@ static bool rep_args(const poporon_t *h, const char *what, size_t count, const R
     return true;
 }
 
-/* the row calls' own checks (poporon_decode_batch_device's, RS handles only) */
-static bool rep_row_args(const poporon_t *h, const char *what, const uint8_t *data, const uint8_t *parity, size_t size,
-                         size_t count, const uint8_t *positions, size_t positions_stride, const uint8_t *counts,
-                         const uint8_t *ok, const RepOut &o)
-{
-    if (!h)
-        return fail("%s: NULL handle", what);
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("%s serves RS handles", what);
-    if (count && (!data || !parity || !ok))
-        return fail("%s: NULL argument", what);
-    if (positions && (!counts || positions_stride < h->rs->num_roots))
-        return fail("%s: erasure batch needs counts and positions_stride >= num_roots", what);
-    if (!check_decode_size(h, size))
-        return fail("%s: size %zu outside [1, %u]", what, size, (unsigned)kmax(h));
-    return rep_args(h, what, count, o);
-}
-
 EXPORT bool poporon_decode_batch_report_device(poporon_t *h, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
                                                size_t parity_stride, size_t size, size_t count,
                                                const uint8_t *d_positions, size_t positions_stride,
@@ -3046,7 +3006,8 @@ EXPORT bool poporon_decode_batch_report_device(poporon_t *h, uint8_t *d_data, si
 {
     const char *what = "poporon_decode_batch_report_device";
     const RepOut o = {d_err_num, d_err_pos, d_err_val, report_stride};
-    if (!rep_row_args(h, what, d_data, d_parity, size, count, d_positions, positions_stride, d_counts, d_ok, o))
+    if (!decode_row_args(h, what, true, d_data, d_parity, size, count, d_positions, positions_stride, d_counts, d_ok) ||
+        !rep_args(h, what, count, o))
         return false;
     if (count == 0)
         return true;
@@ -3054,8 +3015,10 @@ EXPORT bool poporon_decode_batch_report_device(poporon_t *h, uint8_t *d_data, si
         return false;
     BatchScope bsc{h->gpu, (hipStream_t)stream, false};
     DeviceGuard dg(h->gpu.device);
-    return rep_run(h, d_data, data_stride, d_parity, parity_stride, size, count, d_positions, positions_stride,
-                   d_counts, d_ok, d_corrected, o, (hipStream_t)stream);
+    return rep_run(h, {.data = d_data, .ds = data_stride, .par = d_parity, .ps = parity_stride, .size = size,
+                       .count = count, .pos8 = d_positions, .pos_stride = positions_stride, .cnt = d_counts,
+                       .ok = d_ok, .corrected = d_corrected, .s = (hipStream_t)stream},
+                   o);
 }
 
 EXPORT bool poporon_decode_interleaved_report_device(poporon_t *h, uint8_t *d_data, size_t data_stride,
@@ -3102,7 +3065,8 @@ EXPORT bool poporon_decode_batch_report(poporon_t *h, uint8_t *data, size_t data
 {
     const char *what = "poporon_decode_batch_report";
     const RepOut o = {err_num, err_pos, err_val, report_stride};
-    if (!rep_row_args(h, what, data, parity, size, count, positions, positions_stride, counts, ok, o))
+    if (!decode_row_args(h, what, true, data, parity, size, count, positions, positions_stride, counts, ok) ||
+        !rep_args(h, what, count, o))
         return false;
     if (count == 0)
         return true;
@@ -3120,41 +3084,40 @@ EXPORT bool poporon_decode_batch_report(poporon_t *h, uint8_t *data, size_t data
     auto o_num = [&](size_t n) { return o_cor(n) + n; };
     auto o_ep = [&](size_t n) { return rs_ws_round16(o_num(n) + n); };
     auto o_ev = [&](size_t n) { return o_ep(n) + n * nr; };
-    GpuCtx::PipeSlot &ps = h->gpu.rslot;
-    if (!pipe_slot(h, ps, o_ev(chunk) + chunk * nr))
-        return false;
-    for (size_t c0 = 0; c0 < count; c0 += chunk) {
-        const size_t n = std::min(chunk, count - c0);
-        copy_rows(ps.host, w, data + c0 * data_stride, data_stride, size, n);
-        copy_rows(ps.host + size, w, parity + c0 * parity_stride, parity_stride, nr, n);
-        if (positions) {
-            copy_rows(ps.host + o_pos(n), nr, positions + c0 * positions_stride, positions_stride, nr, n);
-            memcpy(ps.host + o_cnt(n), counts + c0, n);
-        }
-        const RepOut d = {ps.dev + o_num(n), ps.dev + o_ep(n), ps.dev + o_ev(n), nr};
-        const bool good =
-            hipMemcpyAsync(ps.dev, ps.host, o_ok(n), hipMemcpyHostToDevice, ps.stream) == hipSuccess &&
-            rep_run(h, ps.dev, w, ps.dev + size, w, size, n, positions ? ps.dev + o_pos(n) : nullptr, nr,
-                    ps.dev + o_cnt(n), ps.dev + o_ok(n), ps.dev + o_cor(n), d, ps.stream) &&
-            hipMemcpyAsync(ps.host, ps.dev, n * w, hipMemcpyDeviceToHost, ps.stream) == hipSuccess &&
-            hipMemcpyAsync(ps.host + o_ok(n), ps.dev + o_ok(n), o_ev(n) + n * nr - o_ok(n), hipMemcpyDeviceToHost,
-                           ps.stream) == hipSuccess;
-        if (!good || hipStreamSynchronize(ps.stream) != hipSuccess) {
-            const std::string msg =
-                g_last_error.empty() ? std::string("HIP failure in a report host batch") : g_last_error;
-            (void)hipStreamSynchronize(ps.stream);
-            return fail("%s", msg.c_str());
-        }
-        copy_rows(data + c0 * data_stride, data_stride, ps.host, w, size, n);
-        copy_rows(parity + c0 * parity_stride, parity_stride, ps.host + size, w, nr, n);
-        memcpy(ok + c0, ps.host + o_ok(n), n);
-        if (corrected)
-            memcpy(corrected + c0, ps.host + o_cor(n), n);
-        memcpy(err_num + c0, ps.host + o_num(n), n);
-        copy_rows(err_pos + c0 * report_stride, report_stride, ps.host + o_ep(n), nr, nr, n);
-        copy_rows(err_val + c0 * report_stride, report_stride, ps.host + o_ev(n), nr, nr, n);
-    }
-    return true;
+    return host_chunks(
+        h, &h->gpu.rslot, 1, count, chunk, o_ev(chunk) + chunk * nr,
+        [&](uint8_t *hb, size_t c0, size_t n) {
+            copy_rows(hb, w, data + c0 * data_stride, data_stride, size, n);
+            copy_rows(hb + size, w, parity + c0 * parity_stride, parity_stride, nr, n);
+            if (positions) {
+                copy_rows(hb + o_pos(n), nr, positions + c0 * positions_stride, positions_stride, nr, n);
+                memcpy(hb + o_cnt(n), counts + c0, n);
+            }
+        },
+        [&](GpuCtx::PipeSlot &ps, size_t n) {
+            uint8_t *dv = ps.dev;
+            HIP_OK(hipMemcpyAsync(dv, ps.host, o_ok(n), hipMemcpyHostToDevice, ps.stream));
+            if (!rep_run(h, {.data = dv, .ds = w, .par = dv + size, .ps = w, .size = size, .count = n,
+                             .pos8 = positions ? dv + o_pos(n) : nullptr, .pos_stride = nr, .cnt = dv + o_cnt(n),
+                             .ok = dv + o_ok(n), .corrected = dv + o_cor(n), .s = ps.stream},
+                         {dv + o_num(n), dv + o_ep(n), dv + o_ev(n), nr}))
+                return false;
+            HIP_OK(hipMemcpyAsync(ps.host, dv, n * w, hipMemcpyDeviceToHost, ps.stream));
+            HIP_OK(hipMemcpyAsync(ps.host + o_ok(n), dv + o_ok(n), o_ev(n) + n * nr - o_ok(n), hipMemcpyDeviceToHost,
+                                  ps.stream));
+            return true;
+        },
+        [&](const uint8_t *hb, size_t c0, size_t n) {
+            copy_rows(data + c0 * data_stride, data_stride, hb, w, size, n);
+            copy_rows(parity + c0 * parity_stride, parity_stride, hb + size, w, nr, n);
+            memcpy(ok + c0, hb + o_ok(n), n);
+            if (corrected)
+                memcpy(corrected + c0, hb + o_cor(n), n);
+            memcpy(err_num + c0, hb + o_num(n), n);
+            copy_rows(err_pos + c0 * report_stride, report_stride, hb + o_ep(n), nr, nr, n);
+            copy_rows(err_val + c0 * report_stride, report_stride, hb + o_ev(n), nr, nr, n);
+        },
+        "HIP failure in a report host batch");
 }
 
 EXPORT bool poporon_amd_erasures_from_mask_device(poporon_t *h, const uint8_t *d_mask, size_t mask_stride, size_t size,
@@ -3697,7 +3660,8 @@ static bool bch_decode_one(poporon_t *h, uint8_t *data, size_t size, uint8_t *pa
         HIP_OK(hipMemcpyAsync(dd, data, db, hipMemcpyHostToDevice, g.stream));
     if (pb)
         HIP_OK(hipMemcpyAsync(dp, parity, pb, hipMemcpyHostToDevice, g.stream));
-    if (!launch_decode(h, dd, db, dp, pb, db, 1, nullptr, 0, nullptr, nullptr, 0, nullptr, dok, dok + 1, g.stream))
+    if (!launch_decode(h, {.data = dd, .ds = db, .par = dp, .ps = pb, .size = db, .count = 1, .ok = dok,
+                           .corrected = dok + 1, .s = g.stream}))
         return false;
     uint8_t res[2];
     uint8_t out[4];
@@ -3750,9 +3714,7 @@ static bool rs_decode_one(poporon_t *h, uint8_t *data, size_t size, uint8_t *par
                 memset(pos + have, 0, (nr - have) * sizeof(uint32_t));
                 *reinterpret_cast<uint32_t *>(z + ZC_CNT) = e->erasure_count;
             }
-            RsCorrParams prm = h->corr;
-            prm.size = (uint32_t)size;
-            prm.pad = (int32_t)(h->rs->gf->field_size - h->rs->num_roots - size);
+            const RsCorrParams prm = corr_params(h, size);
             uint8_t *zd = g.zc_dev;
             const int sv = serve_enabled() && !g.timing && prm.pad == (int32_t)(RS_NN - nr - size)
                                ? srv_call(h, RS_SRV_DECODE, (uint32_t)size, mode)
@@ -3811,9 +3773,7 @@ static bool rs_decode_one(poporon_t *h, uint8_t *data, size_t size, uint8_t *par
                 if (sv == 0)
                     return false;
                 if (sv < 0) {
-                    RsGenParams prm = h->gen;
-                    prm.size = (uint32_t)size;
-                    prm.pad = (int32_t)(nn - nr - size);
+                    const RsGenParams prm = gen_params(h, size);
                     const uint32_t seq = zc_arm(g);
                     KernelTimer t(g, POPORON_AMD_KERNEL_CORRECT, g.stream);
                     HIP_OK(rsgw_decode(g.gtab, &prm, zd + GZ_DATA, size, zd + GZ_PAR, nr, 1, ext, nr, nullptr, pos32,
@@ -3883,8 +3843,10 @@ static bool rs_decode_one(poporon_t *h, uint8_t *data, size_t size, uint8_t *par
                 fail("external syndrome > field size: undefined in the reference, refused");
             } else {
                 HIP_OK(hipMemcpyAsync(g.stage, hs, in_bytes, hipMemcpyHostToDevice, g.stream));
-                if (!launch_decode(h, g.stage, size, g.stage + off_p, nr, size, 1, ext, nr, pos8, pos32,
-                                   pos8 ? nr * 4 : nr, cnt, g.stage + off_ok, g.stage + off_cor, g.stream))
+                if (!launch_decode(h, {.data = g.stage, .ds = size, .par = g.stage + off_p, .ps = nr, .size = size,
+                                       .count = 1, .ext_syn = ext, .ext_stride = nr, .pos8 = pos8, .pos32 = pos32,
+                                       .pos_stride = pos8 ? nr * 4 : nr, .cnt = cnt, .ok = g.stage + off_ok,
+                                       .corrected = g.stage + off_cor, .s = g.stream}))
                     return false;
                 HIP_OK(hipMemcpyAsync(hs, g.stage, off_cor + 1, hipMemcpyDeviceToHost, g.stream));
                 HIP_OK(hipStreamSynchronize(g.stream));

@@ -318,13 +318,16 @@ def test_reserve_and_timing(torch_cuda):
 
 
 def test_host_forms(torch_cuda):
-    """encode_interleaved / decode_interleaved on numpy frames, depth 5 x 300 frames"""
+    """encode_interleaved / decode_interleaved on numpy frames, depth 5 x 300 frames, and x 6503
+    frames: the host forms move 8 MiB of slot bytes at a time, 6502 such frames, so the last
+    frame is a second chunk of its own"""
     h = _handle(RS223)
-    c = _case(RS223, 223, 5, 300)
-    assert (h.encode_interleaved(c["dreg"], 5) == c["preg"]).all()
-    ok, cor, d, p = h.decode_interleaved(c["rd"], c["rp"], 5)
-    ook, ocor, od, op = c["dec"]
-    assert (ok == ook).all() and (cor == ocor).all() and (d == od).all() and (p == op).all()
+    for count in (300, 6503):
+        c = _case(RS223, 223, 5, count)
+        assert (h.encode_interleaved(c["dreg"], 5) == c["preg"]).all()
+        ok, cor, d, p = h.decode_interleaved(c["rd"], c["rp"], 5)
+        ook, ocor, od, op = c["dec"]
+        assert (ok == ook).all() and (cor == ocor).all() and (d == od).all() and (p == op).all()
     # erasure form through the host path
     rd, rp, pos, cnt, (ook, ocor, od, op) = _erasure_case(RS223, 223, 4, 50, False)
     ok, cor, d, p = h.decode_interleaved(rd, rp, 4, positions=pos, counts=cnt)

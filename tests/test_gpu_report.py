@@ -467,9 +467,10 @@ def test_reserve_report(torch_cuda):
 
 
 def test_host_form(torch_cuda):
-    """decode_batch_report on numpy rows, error and erasure mode"""
+    """decode_batch_report on numpy rows, error and erasure mode; 25,972 rows are two chunks (the host
+    form moves 8 MiB of slot bytes at a time: 25,971 rows of 255 + 4 + 64 bytes), the second of one row"""
     h = _handle(RS223)
-    for c in (_random_case(RS223, 223, 257), _erasure_case(RS223, 223, "short")):
+    for c in (_random_case(RS223, 223, 257), _erasure_case(RS223, 223, "short"), _random_case(RS223, 223, 25972)):
         d, p, ok, cor, num, epos, evl = h.decode_batch_report(c["data"], c["parity"], c["pos"], c["cnt"])
         for got, want in ((d, "od"), (p, "op"), (ok, "ok"), (cor, "cor"), (num, "num"), (epos, "epos"), (evl, "evl")):
             assert (got == c[want]).all(), want

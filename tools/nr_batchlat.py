@@ -2,7 +2,7 @@
 """Wall time per errors-only device decode call of a byte-symbol code with
 fewer than 32 roots, general kernel (rs_generic.hip) against the split
 kernels (POPORON_AMD_DECODE_PATH=split, npar = nr), over batch sizes: where
-the split path starts to pay (api.cpp launch_decode, h->nrsplit).
+the split path starts to pay (api.cpp decode_route, h->nrsplit).
 
     python tools/nr_batchlat.py [--params 8,0x11D,1,1,16] [--reps 20]"""
 import argparse
