@@ -336,9 +336,13 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
  * Omega, 5 = Chien, 6 = Forney, 8 = apply, 7 = the one-codeword-per-wave
  * decoder over the codewords the split kernels hand on (for batches routed
  * by their size Forney and the apply are one launch, charged to 8, and 6
- * records none; they are two launches, 6 and 8, under
- * POPORON_AMD_DECODE_PATH=split, and POPORON_AMD_DECODE_TAIL=fused / split in
- * the environment at poporon_create chooses either way).  Erasure-mode
+ * records none; from more than 1024 codewords per compute unit on the root
+ * search runs in that launch too and 5 records none either; Forney and the
+ * apply are two launches, 6 and 8, under POPORON_AMD_DECODE_PATH=split, and
+ * POPORON_AMD_DECODE_TAIL=search / fused / split in the environment at
+ * poporon_create chooses the tail at every count: search = the one launch
+ * charged to 8, fused = 5, then Forney and the apply as one launch charged to
+ * 8, split = 5, 6 and 8).  Erasure-mode
  * batches of that size: 1, 9 = the 32-sorted-erasure kernel (prim 1), 4 / 5
  * / 6 = the errata kernels, 7 = the same per-wave decoder over the rest, 8 =
  * apply.  A batch of one codeword: 10 = the one-workgroup decoder

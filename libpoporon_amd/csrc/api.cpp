@@ -212,7 +212,9 @@ struct _poporon_t {
     int decode_path; /* 0: by batch size, 1: split kernels (rs_fast.hip), 2: single kernel (rs_correct_k),
                       * 3: one codeword per wave (rs_wave_k) */
     int decode_tail; /* split kernels: 0 Forney and apply in one kernel (rs_forney_apply_k), 1 rs_forney_k then
-                      * rs_apply_k; POPORON_AMD_DECODE_TAIL=fused|split, default: fused where the batch size
+                      * rs_apply_k, 2 the root search, Forney and apply in one kernel (rs_search_apply_k), 3 by
+                      * the count: 2 where a workgroup of it has more than one batch, else 0 (split_tail);
+                      * POPORON_AMD_DECODE_TAIL=fused|split|search, default: by the count where the batch size
                       * chooses the path, every stage its own kernel under POPORON_AMD_DECODE_PATH=split */
     bool generic;   /* served by the general-parameter kernels (rs_generic.hip) */
     bool lfsr_nr;   /* generic code, num_roots <= 32: batch encodes on the LFSR kernel (rsk_encode_nr) */
@@ -619,7 +621,11 @@ static void build_decode_tables(poporon_t *h, uint32_t nr)
     const char *dp = getenv("POPORON_AMD_DECODE_PATH");
     h->decode_path = !dp ? 0 : !strcmp(dp, "split") ? 1 : !strcmp(dp, "single") ? 2 : !strcmp(dp, "wave") ? 3 : 0;
     const char *dt = getenv("POPORON_AMD_DECODE_TAIL");
-    h->decode_tail = dt && !strcmp(dt, "split") ? 1 : dt && !strcmp(dt, "fused") ? 0 : h->decode_path == 1 ? 1 : 0;
+    h->decode_tail = dt && !strcmp(dt, "split")    ? 1
+                     : dt && !strcmp(dt, "fused")  ? 0
+                     : dt && !strcmp(dt, "search") ? 2
+                     : h->decode_path == 1         ? 1
+                                                   : 3;
 }
 
 /* General-parameter kernels: byte symbols (2 <= m <= 8) and 1 <= num_roots
@@ -1840,6 +1846,21 @@ static hipError_t launch_list_nr(poporon_t *h, const DecodeCall &c, const RsSpli
                        c.corrected, ws.list, ws.nlist, nullptr, 0u, g.num_cu, c.s);
 }
 
+/* How the split decode ends (decode_tail).  Left to the count, rs_search_apply_k takes the batches that
+ * give its one workgroup per CU more than one 1024-row batch, the ones whose waves have a next batch to
+ * search while a block's rows are in flight: 0.130 against 0.171 ms at 2^20 rows.  Smaller batches keep
+ * rs_chien_k and rs_forney_apply_k, the launches that the recorded route table
+ * (tests/golden/decode_routes.json) names for them; the one kernel measured 4-5 us shorter there as well
+ * (33 against 38 us at 16,384 rows, profiles/search_tail_counts.log), a gain left for a change that
+ * records the table anew.  POPORON_AMD_DECODE_TAIL=search takes it at every count. */
+static int split_tail(const poporon_t *h, size_t count)
+{
+    if (h->decode_tail != 3)
+        return h->decode_tail;
+    const size_t cus = (size_t)(h->gpu.num_cu > 0 ? h->gpu.num_cu : 256);
+    return count > cus * 1024u ? 2 : 0;
+}
+
 /* ROUTE_SPLIT: the split error-mode decode (rs_fast.hip, one codeword per
  * lane; what it hands on: one codeword per wave); fewer than 32 roots: the
  * _nr kernels, the list on the general kernel */
@@ -1864,8 +1885,15 @@ static bool launch_split(poporon_t *h, const DecodeCall &c)
     STAGE(g, POPORON_AMD_KERNEL_BM, s,
           nr ? rsk_bm_nr(g.tab, &ws, c.count, npar, c.ok, c.corrected, g.num_cu, s)
              : rsk_bm(g.tab, &ws, c.count, c.ok, c.corrected, g.num_cu, s));
-    STAGE(g, POPORON_AMD_KERNEL_CHIEN, s, rsk_chien(g.tab, &prm, &ws, c.count, c.ok, c.corrected, g.num_cu, s));
-    if (h->decode_tail == 0) {
+    const int tail = split_tail(h, c.count);
+    if (tail != 2)
+        STAGE(g, POPORON_AMD_KERNEL_CHIEN, s, rsk_chien(g.tab, &prm, &ws, c.count, c.ok, c.corrected, g.num_cu, s));
+    if (tail == 2) {
+        /* the root search too (rs_search_apply_k), charged to the apply's id: the Chien id records no launch */
+        STAGE(g, POPORON_AMD_KERNEL_APPLY, s,
+              rsk_search_apply(g.tab, &prm, &ws, c.data, c.ds, c.par, c.ps, c.count, npar, c.ok, c.corrected, g.num_cu,
+                               s));
+    } else if (tail == 0) {
         /* Forney and the block apply in one kernel (rs_forney_apply_k), charged to the apply's id */
         STAGE(g, POPORON_AMD_KERNEL_APPLY, s,
               rsk_forney_apply(g.tab, &prm, &ws, c.data, c.ds, c.par, c.ps, c.count, npar, c.ok, c.corrected, g.num_cu,

@@ -311,6 +311,11 @@ hipError_t rsk_apply(const RsCorrParams *prm, const RsSplitWs *ws, uint8_t *data
 hipError_t rsk_forney_apply(const RsDevTables *tab, const RsCorrParams *prm, const RsSplitWs *ws, uint8_t *data,
                             size_t dstride, uint8_t *parity, size_t pstride, size_t count, uint32_t npar, uint8_t *ok,
                             uint8_t *corrected, int num_cu, hipStream_t stream);
+/* rsk_chien and rsk_forney_apply in one kernel (api.cpp decode_tail 2): the root lists stay in registers too,
+ * ws.roots is not written; everything else is left as the two launches leave it */
+hipError_t rsk_search_apply(const RsDevTables *tab, const RsCorrParams *prm, const RsSplitWs *ws, uint8_t *data,
+                            size_t dstride, uint8_t *parity, size_t pstride, size_t count, uint32_t npar, uint8_t *ok,
+                            uint8_t *corrected, int num_cu, hipStream_t stream);
 
 /*
  * The same split decode for a byte-symbol code of npar < 32 roots (tab from

@@ -9,6 +9,11 @@
  *   rs_bm_k      syndromes -> Berlekamp-Massey (src/decode.c:49-96) -> Lambda,
  *                degree (:98-110), Omega (:147-158)
  *   rs_chien_k   Lambda -> root map over the 255 points (:112-145)
+ *   rs_search_apply_k  rs_chien_k and rs_forney_apply_k in one launch, one
+ *                software pipeline per wave (the tail of the batches routed
+ *                by their size that give a CU more than one 1024-row batch;
+ *                160 KiB of LDS, one workgroup per CU); as two for smaller
+ *                batches and with POPORON_AMD_DECODE_TAIL=fused:
  *   rs_forney_apply_k  roots, Omega, Lambda -> Forney magnitudes (:159-191)
  *                and the corrections (:215-226) in one launch; as two,
  *                rs_forney_k and rs_apply_k<16>, with POPORON_AMD_DECODE_TAIL=split
@@ -953,8 +958,8 @@ __global__ __launch_bounds__(AWG) void rs_apply_k(const uint8_t *__restrict__ me
  * positions and 16 magnitudes packed bytewise (a magnitude 0 corrects
  * nothing); returns the number of corrections.  (rs_forney_k keeps its own
  * copy: calling this from it costs it 2 VGPRs, and scratch for P11 = false.) */
-template <bool P11>
-__device__ __forceinline__ uint32_t forney_lane(const GfA gf, const uint32_t fcr, const uint32_t iprim,
+template <bool P11, class G = GfA> /* G: where the table sits (GfA: at LDS address 0; GfAt<B>: at B) */
+__device__ __forceinline__ uint32_t forney_lane(const G gf, const uint32_t fcr, const uint32_t iprim,
                                                 const int32_t pad, uint32_t deg, const uint4 o4, const uint4 l4,
                                                 const uint32_t (&rl)[4], uint32_t (&posp)[4], uint32_t (&magp)[4])
 {
@@ -1147,6 +1152,382 @@ __global__ __launch_bounds__(FAWG, FAWG / 256) void rs_forney_apply_k(
 }
 
 /* ------------------------------------------------------------------------ */
+/* rs_search_apply_k: root search, magnitudes and corrections in one kernel  */
+/* ------------------------------------------------------------------------ */
+
+/*
+ * rs_chien_k and rs_forney_apply_k as one kernel: the root search is pure
+ * LDS / VALU work and needs no row, the apply is the decode's only HBM
+ * stream, and run back to back each leaves the other's unit idle.  Here every
+ * wave carries both over its batches b (64 rows), last batches first:
+ *
+ *   prologue  search(b0)                      -> root list in 4 VGPRs
+ *   loop b    request the first half of block b (2 quarters, 32 VGPRs)
+ *             Forney(b)                       forney_lane; the loads fly
+ *             stage, XOR, store the first half
+ *             request the second half         (the same 32 VGPRs)
+ *             search(b + 1)                   rs_chien_k's body; the loads fly
+ *             stage, XOR, store the second half
+ *
+ * so each half of a block's reads has a compute phase of the same wave to
+ * return under.  No wave waits for another one: no flags, no workgroup
+ * barrier after the table fill.  A row the search rejects is finished there
+ * (ok = corrected = 0, RS_ST_DONE) and leaves the wave's fast set: its bytes
+ * go back unchanged.  Loads that a later wait counts past are issued on every
+ * path (next batch's meta and Lambda from row 0, the row quarters from the
+ * table image where there is no block to read), so the number in flight is
+ * known at compile time.  ws->roots is not written: the root lists stay in
+ * registers and nothing behind the tail reads them.
+ *
+ * LDS, all 160 KiB (the one array sits at address 0, as rs_chien_k's table):
+ *   SA_CH  the Chien rows e < 255 at their rs_chien_k addresses e * 256 + ...
+ *   SA_GF  the GF image, 65,280 B up: inside the 16-bit offset field of the DS
+ *          reads, so GfAt adds it for free (the address forms stored in the
+ *          table and pofs stay those of a table at 0)
+ *   SA_ST  2 KiB per wave: a quarter block (4,080 B) goes through it as two
+ *          byte windows of 2,048 and 2,032 B, each taking the corrections whose
+ *          offset (lane & 15) * 255 + p falls in it; during the search it holds
+ *          the lanes' root lists (16 B each).  The corrections of a quarter's
+ *          16 rows are spread over all 64 lanes first (ds_bpermute): XORed in
+ *          by the 16 owning lanes, 16 predicated steps per window, the staging
+ *          cost 0.023 ms of VALU issue (profiles/search_tail_variants.log)
+ *   SA_Z   the all-zero rows of zero coefficients: they step by WRAP, which
+ *          chien_step maps back onto itself from any address
+ */
+#define SAWG 1024
+#define SA_CH 0u
+#define SA_GF (255u * 256u)
+#define SA_ST (SA_GF + 65536u)
+#define SA_WIN 2048u
+#define SA_Z (SA_ST + (SAWG / 64) * SA_WIN)
+#define SA_END (SA_Z + 256u)
+
+/* GfA for a table image at LDS byte address B <= 65535 */
+template <uint32_t B>
+struct GfAt : GfA {
+    __device__ __forceinline__ uint32_t expa(uint32_t a) const { return lds8(a + B); }
+    __device__ __forceinline__ uint32_t loga(uint32_t v) const { return lds16(pofs + 1u + (v << 7) + B); }
+    __device__ __forceinline__ uint32_t logs(uint32_t v) const { return loga(v) - pofs; }
+    __device__ __forceinline__ uint32_t exp(uint32_t l) const { return lds8(pofs + (l << 7) + B); }
+};
+
+__device__ __forceinline__ void wave_sync_lds()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+/* rs_chien_k's search, statement for statement, for one codeword per lane
+ * (fast: on the fast path with Lambda's logs in l4; every other lane passes
+ * all-zero coefficients).  The root list (flag-bit indices, root_point()) is
+ * built in the lane's 16 LDS bytes at lp0 and returned in rl; rejected rows
+ * are finished here (row cw of meta, ok and corrected: the wave's pointers
+ * and the lane).  Returns whether the row stays on the fast path. */
+__device__ __forceinline__ bool search_lane(const RsCorrParams &P, const bool fast, const uint32_t deg, const uint4 l4,
+                                            const uint32_t lp0, const uint32_t cw, uint8_t *__restrict__ meta,
+                                            uint8_t *__restrict__ ok, uint8_t *__restrict__ corrected,
+                                            uint32_t (&rl)[4])
+{
+    constexpr uint32_t WRAP = 255u * 256u;
+    uint32_t lr = threadIdx.x & 15u;
+    asm volatile("" : "+v"(lr));
+    uint32_t D[4] = {l4.x, l4.y, l4.z, l4.w};
+    uint32_t E[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        E[k] = (lr & 4u) ? D[(k + 1) & 3] : D[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        D[k] = (lr & 8u) ? E[(k + 2) & 3] : E[k];
+    uint32_t R[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        R[k] = __builtin_amdgcn_alignbyte(D[(k + 1) & 3], D[k], lr & 3u);
+    /* the setup's constants from a zero made here: as plain constants they are hoisted out of the batch
+     * loop into VGPRs that stay live across the Forney phase, and the kernel spills */
+    uint32_t oz = 0;
+    asm volatile("" : "+v"(oz));
+    const uint32_t zrow = oz + SA_Z, wrap = oz + WRAP;
+    uint32_t A[16], inc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t jm = ((uint32_t)k + lr) & 15u; /* j_k - 1 */
+        const uint32_t e = (R[k >> 2] >> (8 * (k & 3))) & 0xffu;
+        A[k] = (e == 255u ? zrow : SA_CH + (e << 8)) + (jm << 4);
+        inc[k] = e == 255u ? wrap : (jm == 15u ? 256u : (jm + 1u) << 12);
+    }
+    *(__attribute__((address_space(3))) lds_u32x4_t *)(size_t)lp0 = lds_u32x4_t{oz, oz, oz, oz};
+    uint32_t lp = lp0;
+    uint32_t cnt = 0, z0 = 0;
+    auto push = [&](uint32_t v) __attribute__((always_inline)) {
+        lds_st8(lp, v);
+        lp += 1u;
+    };
+#pragma unroll 1
+    for (int w = 0; w < 8; ++w) {
+        uint32_t word = 0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            uint32_t acc[4] = {0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};
+#pragma unroll
+            for (int k = 0; k < 16; k += 2) {
+                const lds_u32x4_t r1 = lds128(A[k]), r2 = lds128(A[k + 1]);
+                A[k] = chien_step<WRAP>(A[k], inc[k]);
+                A[k + 1] = chien_step<WRAP>(A[k + 1], inc[k + 1]);
+                acc[0] = xor3(acc[0], r1.x, r2.x);
+                acc[1] = xor3(acc[1], r1.y, r2.y);
+                acc[2] = xor3(acc[2], r1.z, r2.z);
+                acc[3] = xor3(acc[3], r1.w, r2.w);
+            }
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+                word = __builtin_amdgcn_bitop3_b32(word, zero80(acc[d]) >> (d + 4 * h), 0u, 0xF0 | 0xCC);
+        }
+        if (w == 7)
+            word &= ~(1u << 24); /* i' = 255 (point 31: bit 24) repeats i' = 0 */
+        if (w == 0) {
+            z0 = (word >> 7) & 1u; /* i' = 0 (bit 7) is the reference's last point, i = 255 */
+            word &= ~0x80u;
+        }
+        cnt += __popc(word);
+        const uint32_t wb = 32u * (uint32_t)w;
+        while (word != 0u) { /* at most deg <= 16 pushes per lane in all */
+            const uint32_t b = __builtin_ctz(word);
+            word &= word - 1u;
+            push(wb | b);
+        }
+    }
+    if (z0)
+        push(248u); /* flag bit 24 of word 7: root_point() = 255 */
+    cnt += z0;
+    const lds_u32x4_t l4r = lds128(lp0);
+    rl[0] = l4r.x, rl[1] = l4r.y, rl[2] = l4r.z, rl[3] = l4r.w;
+    bool good = cnt == deg; /* src/decode.c:143-145 */
+    if (P.pad > 0) {
+        /* locations k = (i iprim - 1) mod 255 below pad fail, src/decode.c:132-134 */
+        bool low = false;
+#pragma unroll
+        for (int n = 0; n < 16; ++n) {
+            const uint32_t i = root_point((rl[n >> 2] >> (8 * (n & 3))) & 0xffu);
+            low |= (uint32_t)n < cnt && (int32_t)((i * P.iprim + 254u) % 255u) < P.pad;
+        }
+        good = good && !low;
+    }
+    if (fast && !good) {
+        ok[cw] = 0;
+        if (corrected)
+            corrected[cw] = 0;
+        meta[cw] = (uint8_t)(RS_ST_DONE << 5);
+    }
+    return fast && good;
+}
+
+template <bool P11>
+__global__ __launch_bounds__(SAWG, SAWG / 256) void rs_search_apply_k(
+    const RsDevTables *__restrict__ T, RsCorrParams P, uint8_t *data, size_t dstride, uint8_t *parity, size_t pstride,
+    size_t count, const uint8_t *__restrict__ lam, const uint8_t *__restrict__ om, uint8_t *__restrict__ meta,
+    uint8_t *__restrict__ ok, uint8_t *__restrict__ corrected, uint32_t wire, uint32_t npar)
+{
+    static_assert(SA_END == 163840u && SA_GF <= 65535u, "the whole LDS; the GF image inside the DS offset field");
+    __shared__ uint4 lds[SA_END / 16];
+    {
+        constexpr uint32_t NCH = 255u * 16u; /* every load first, then the stores */
+        uint4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t t = min(threadIdx.x + k * SAWG, NCH - 1u);
+            v[k] = T->chien[(t & 15u) * 256u + (t >> 4)];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (threadIdx.x + k * SAWG < NCH)
+                lds[SA_CH / 16 + threadIdx.x + k * SAWG] = v[k];
+        if (threadIdx.x < 16u)
+            lds[SA_Z / 16 + threadIdx.x] = make_uint4(0, 0, 0, 0);
+    }
+    fill_gfa<SAWG>(reinterpret_cast<uint32_t *>(lds + SA_GF / 16), T);
+    __syncthreads();
+    const GfAt<SA_GF> gf{4u * (threadIdx.x & 31u) + 1u};
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint4 *st = lds + SA_ST / 16 + wv * (SA_WIN / 16);
+    uint32_t *stw = reinterpret_cast<uint32_t *>(st);
+    const uint32_t lp0 = SA_ST + wv * SA_WIN + 16u * lane; /* the lane's root list during the search */
+    /* positions past the codeword are never written (rs_apply_k) */
+    const uint32_t lim = P.size + npar;
+    const uint4 none = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    const lds_u32x4_t *img = reinterpret_cast<const lds_u32x4_t *>(T->gfa);
+    /* chunk lane + 64 k of a quarter; lane 63 has no fourth one and reads chunk 254 again */
+    const uint32_t c3 = min(lane + 192u, FAQ - 1u);
+
+    /* one quarter block through the wave's window, in two byte windows; pq / mq: the corrections as all 64
+     * lanes share them (below), lane l those of the quarter's row l & 15 */
+    const uint32_t rofs = (lane & 15u) * 255u;
+    auto stage_quarter = [&](const uint32_t q, const lds_u32x4_t (&vq)[4], lds_u32x4_t *rows, const uint32_t pq,
+                             const uint32_t mq) __attribute__((always_inline)) {
+#pragma unroll
+        for (uint32_t wn = 0; wn < 2; ++wn) {
+#pragma unroll
+            for (uint32_t j = 0; j < 2; ++j) {
+                const uint32_t k = 2u * wn + j;
+                if (lane + 64u * k < FAQ)
+                    st[lane + 64u * j] = make_uint4(vq[k].x, vq[k].y, vq[k].z, vq[k].w);
+            }
+            wave_sync_lds();
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const uint32_t mg = (mq >> (8 * n)) & 0xffu;
+                const uint32_t p = (pq >> (8 * n)) & 0xffu;
+                /* p < 255: inside the row of the quarter */
+                const uint32_t a = rofs + p;
+                if (mg && p < lim && (a >> 11) == wn)
+                    atomicXor(stw + ((a & (SA_WIN - 1u)) >> 2), mg << (8u * (a & 3u)));
+            }
+            wave_sync_lds();
+#pragma unroll
+            for (uint32_t j = 0; j < 2; ++j) {
+                const uint32_t k = 2u * wn + j;
+                if (lane + 64u * k < FAQ) {
+                    const uint4 r = st[lane + 64u * j];
+                    __builtin_nontemporal_store(lds_u32x4_t{r.x, r.y, r.z, r.w}, rows + FAQ * q + lane + 64u * k);
+                }
+            }
+            wave_sync_lds();
+        }
+    };
+
+    /* Waves by index wi = cw / 64 (below 2^32: the launcher refuses more rows): wi < cq is a whole wave,
+     * wi == cq the last partial one of cr rows.  Everything per wave is scalar, and every row address a
+     * scalar base plus the lane: no 64-bit value per lane across the phases. */
+    const uint32_t nb = (uint32_t)((count + SAWG - 1) / SAWG), cq = (uint32_t)(count >> 6), cr = (uint32_t)count & 63u;
+    auto rows_of = [&](const uint32_t wi) __attribute__((always_inline)) { /* valid rows of wave wi */
+        return wi < cq ? 64u : wi == cq ? cr : 0u;
+    };
+
+    /* prologue: the search of the first batch (the grid never exceeds nb) */
+    uint32_t b = blockIdx.x;
+    uint32_t wi = (nb - 1u - b) * (SAWG / 64) + wv, nrow = rows_of(wi);
+    uint32_t deg;
+    bool fast;
+    uint32_t rl[4] = {0, 0, 0, 0};
+    {
+        const size_t wbase = (size_t)wi * 64u;
+        const uint32_t mt = lane < nrow ? meta[wbase + lane] : 0u;
+        fast = (mt >> 5) == RS_ST_FAST;
+        deg = fast ? (mt & 31u) : 0u;
+        if (__ballot(fast) != 0ull) {
+            const uint4 l4 = fast ? reinterpret_cast<const uint4 *>(lam)[wbase + lane] : none;
+            fast = search_lane(P, fast, deg, l4, lp0, lane, meta + wbase, ok + wbase,
+                               corrected ? corrected + wbase : nullptr, rl);
+            wave_sync_lds();
+            deg = fast ? deg : 0u; /* a rejected row corrects nothing */
+        }
+    }
+
+    for (;;) {
+        /* last batches first: the codewords the syndrome pass read last may still sit in the MALL */
+        const size_t wbase = (size_t)wi * 64u;
+        const uint32_t bn = b + gridDim.x;
+        const bool more = bn < nb; /* uniform, as everything of the next wave but its lanes' state */
+        const bool block = wire && nrow == 64u && __ballot(fast) != 0ull;
+        const uint32_t nwi = more ? (nb - 1u - bn) * (SAWG / 64) + wv : 0u, nnrow = more ? rows_of(nwi) : 0u;
+        /* loads that later waits count past are issued on every path, from row 0 where there is none */
+        const size_t nwbase = nnrow ? (size_t)nwi * 64u : 0u, cbase = nrow ? wbase : 0u;
+        const uint32_t nl = lane < nnrow ? lane : 0u, cl = lane < nrow ? lane : 0u;
+        /* Omega and Lambda of this batch and the next one's state, then the first two quarters */
+        uint4 o4 = (reinterpret_cast<const uint4 *>(om) + cbase)[cl];
+        uint4 l4 = (reinterpret_cast<const uint4 *>(lam) + cbase)[cl];
+        uint32_t nmt = (meta + nwbase)[nl];
+        lds_u32x4_t *rows = reinterpret_cast<lds_u32x4_t *>(data + wbase * 255u);
+        const lds_u32x4_t *pre = block ? rows : img;
+        lds_u32x4_t v[2][4];
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k)
+                v[q][k] = __builtin_nontemporal_load(pre + FAQ * q + (k < 3 ? lane + 64u * k : c3));
+        __builtin_amdgcn_sched_barrier(0);
+        if (!fast)
+            o4 = l4 = none;
+        uint32_t posp[4], magp[4];
+        const uint32_t fixed = forney_lane<P11>(gf, P.fcr, P.iprim, P.pad, deg, o4, l4, rl, posp, magp);
+        if (fast) {
+            (ok + wbase)[lane] = 1;
+            if (corrected)
+                (corrected + wbase)[lane] = (uint8_t)fixed;
+        }
+        /* The corrections of a quarter's 16 rows spread over all 64 lanes: lane l takes dword l >> 4 (four
+         * locations, four magnitudes) of row l & 15, lane 16 q + (l & 15)'s, so that the XOR below runs 4
+         * steps on every lane and not 16 on a quarter of them.  Other layouts and a batch's last partial
+         * wave correct byte by byte, here, before the search needs the registers. */
+        uint32_t pq[4] = {0, 0, 0, 0}, mq[4] = {0, 0, 0, 0};
+        if (block) {
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) {
+                const int src = (int)(4u * (16u * q + (lane & 15u)));
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k) {
+                    const uint32_t pk = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)posp[k]);
+                    const uint32_t mk = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)magp[k]);
+                    pq[q] = (lane >> 4) == k ? pk : pq[q];
+                    mq[q] = (lane >> 4) == k ? mk : mq[q];
+                }
+            }
+        } else if (fast) {
+            const size_t cw = wbase + lane;
+            uint8_t *cdata = data + cw * dstride, *cpar = parity + cw * pstride;
+#pragma unroll
+            for (int n = 0; n < 16; ++n) {
+                const uint32_t mg = (magp[n >> 2] >> (8 * (n & 3))) & 0xffu;
+                const uint32_t p = (posp[n >> 2] >> (8 * (n & 3))) & 0xffu;
+                if (mg && p < lim) {
+                    uint8_t *d = p < P.size ? cdata + p : cpar + (p - P.size);
+                    *d = (uint8_t)(*d ^ mg);
+                }
+            }
+        }
+        /* the next batch's Lambda ahead of this block's stores and second half */
+        nmt = lane < nnrow ? nmt : 0u;
+        bool nfast = (nmt >> 5) == RS_ST_FAST;
+        const uint32_t ndeg = nfast ? (nmt & 31u) : 0u;
+        uint4 nl4 = (reinterpret_cast<const uint4 *>(lam) + nwbase)[nl];
+        __builtin_amdgcn_sched_barrier(0);
+        if (block) {
+            stage_quarter(0u, v[0], rows, pq[0], mq[0]);
+            stage_quarter(1u, v[1], rows, pq[1], mq[1]);
+        }
+        const lds_u32x4_t *pre2 = block ? rows + 2u * FAQ : img;
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k)
+                v[q][k] = __builtin_nontemporal_load(pre2 + FAQ * q + (k < 3 ? lane + 64u * k : c3));
+        __builtin_amdgcn_sched_barrier(0);
+        if (!nfast)
+            nl4 = none;
+        /* (skipped: no row of the next batch is fast, and its stale root list is never read) */
+        if (__ballot(nfast) != 0ull) { /* uniform; false past the last batch */
+            nfast = search_lane(P, nfast, ndeg, nl4, lp0, lane, meta + nwbase, ok + nwbase,
+                                corrected ? corrected + nwbase : nullptr, rl);
+            wave_sync_lds();
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (block) {
+            stage_quarter(2u, v[0], rows, pq[2], mq[2]);
+            stage_quarter(3u, v[1], rows, pq[3], mq[3]);
+        }
+        if (!more)
+            break;
+        b = bn;
+        wi = nwi;
+        nrow = nnrow;
+        fast = nfast;
+        deg = nfast ? ndeg : 0u; /* a rejected row corrects nothing */
+    }
+}
+
+/* ------------------------------------------------------------------------ */
 /* launchers                                                                 */
 /* ------------------------------------------------------------------------ */
 
@@ -1220,6 +1601,29 @@ extern "C" hipError_t rsk_forney_apply(const RsDevTables *tab, const RsCorrParam
     else
         RS_LAUNCH(rs_forney_apply_k<false>, grid, dim3(FAWG), 0, stream, tab, *prm, data, dstride, parity, pstride,
                   count, ws->lam, ws->om, ws->roots, ws->meta, ok, corrected, wire, npar);
+    return hipGetLastError();
+}
+
+/* rsk_chien and rsk_forney_apply in one launch (ws.roots is not written) */
+extern "C" hipError_t rsk_search_apply(const RsDevTables *tab, const RsCorrParams *prm, const RsSplitWs *ws,
+                                       uint8_t *data, size_t dstride, uint8_t *parity, size_t pstride, size_t count,
+                                       uint32_t npar, uint8_t *ok, uint8_t *corrected, int num_cu, hipStream_t stream)
+{
+    if (count == 0)
+        return hipSuccess;
+    if (count >> 38) /* the kernel counts waves in 32 bits */
+        return hipErrorInvalidValue;
+    const uint32_t wire = prm->size + npar == 255u && dstride == 255u && pstride == 255u &&
+                          parity == data + prm->size && (reinterpret_cast<uintptr_t>(data) & 15u) == 0u;
+    /* one workgroup per CU, each looping over its batches, as rsk_forney_apply */
+    const size_t need = (count + SAWG - 1) / SAWG, cap = (size_t)(num_cu > 0 ? num_cu : 256);
+    const dim3 grid((uint32_t)(need < cap ? need : cap));
+    if (prm->fcr == 1u && prm->iprim == 1u)
+        RS_LAUNCH(rs_search_apply_k<true>, grid, dim3(SAWG), 0, stream, tab, *prm, data, dstride, parity, pstride,
+                  count, ws->lam, ws->om, ws->meta, ok, corrected, wire, npar);
+    else
+        RS_LAUNCH(rs_search_apply_k<false>, grid, dim3(SAWG), 0, stream, tab, *prm, data, dstride, parity, pstride,
+                  count, ws->lam, ws->om, ws->meta, ok, corrected, wire, npar);
     return hipGetLastError();
 }
 
