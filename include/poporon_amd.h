@@ -181,6 +181,67 @@ bool poporon_decode_interleaved(poporon_t *pprn, uint8_t *data, size_t data_stri
                                 uint8_t *corrected);
 bool poporon_amd_reserve_interleaved(poporon_t *pprn, size_t max_codewords);
 
+/* ---- wire form of the interleaved calls ----------------------------------------
+ * A CCSDS 131.0-B frame does not carry the code's bytes: its symbols travel in
+ * Berlekamp's dual-basis representation, and the block is XORed with the
+ * pseudo-randomizer.  A handle's wire form says how a byte of a frame becomes
+ * a byte of the code: a symbol map, to_code[256] with its inverse to_wire[256],
+ * and a receive-side XOR sequence of xor_len bytes.  It is applied inside the
+ * layout kernels of the interleaved calls and costs no pass over the frames.
+ *
+ * poporon_amd_set_wire_form: RS handles of symbol_size 8 (others: false with a
+ * message).  to_code and to_wire are both NULL (the identity) or both given
+ * with to_wire[to_code[v]] == v for all 256 v; xor_seq NULL with xor_len 0 is
+ * no sequence, else 1 <= xor_len <= 65536; anything else fails and leaves the
+ * form as it was.  All NULL / 0 clears the form.  The tables are copied.
+ * poporon_amd_set_wire_form_ccsds computes the CCSDS tables from their
+ * definitions on any symbol_size 8 handle (the code they belong to is
+ * symbol_size 8, polynomial 0x187, first root 112, primitive element 11, 32
+ * roots): dual_basis, over the field 0x187 with alpha = 2, beta = alpha^117 and
+ * Tr(a) = a + a^2 + ... + a^128, bit 7-i of to_wire[u] is Tr(u beta^i), and
+ * to_code is the inverse table; randomizer is the 255 bytes of h(x) = x^8 + x^7
+ * + x^5 + x^3 + 1 from the all-ones state, MSB first.  Neither of the two
+ * clears the form.  poporon_amd_get_wire_form returns false when no form is
+ * set, else copies out what was set: the identity for maps that were not
+ * given, *xor_len (0 without a sequence) and, when xor_seq is not NULL, the
+ * sequence (xor_cap < *xor_len: false, *xor_len still written).
+ *
+ * Set and get need no GPU.  The device copy is made by the next interleaved
+ * call or by poporon_amd_reserve_interleaved, after which calls with the form
+ * set allocate nothing.  Setting is a setup call: it waits by itself for the
+ * work this handle has enqueued before the device tables are replaced, so
+ * calls enqueued before it keep the old form and the caller never
+ * synchronises around it.
+ *
+ * The form is applied by poporon_{encode,decode,check}_interleaved_device,
+ * poporon_{encode,decode}_interleaved and
+ * poporon_decode_interleaved_report_device, at every depth, 1 included (which
+ * then runs through the staging rows too); NOT by the row *_batch* calls, the
+ * single calls, the syndrome calls or poporon_amd_erasures_from_mask_device.
+ * Rows in wire form go through the interleaved calls at depth 1.
+ *
+ * A byte's block offset b is its offset in the message region, or size*depth
+ * plus its offset in the parity region: wire-block order, wherever the two
+ * regions lie.
+ *  - decode / check: the code byte is to_code[wire ^ xor_seq[b % xor_len]], and
+ *    the row kernels see those.  d_ok, d_corrected, d_dirty and erasure lists
+ *    mean what they mean without a form.
+ *  - after a decode both regions hold to_wire[code byte], for every codeword,
+ *    decoded or not: the block comes back derandomized and is not randomized
+ *    again; a failed codeword is otherwise unchanged.
+ *  - encode: the message is read through to_code and the parity written
+ *    through to_wire.  The sequence is NOT used: the message region is const,
+ *    and the randomizer is the last transmit step over the finished block,
+ *    which the caller XORs.
+ *  - report form: d_err_pos is as without a form; d_err_val is before XOR
+ *    after of the CODE bytes (the diff of the staging rows).  To undo a
+ *    correction in the returned row: to_wire[to_code[returned] ^ d_err_val]. */
+bool poporon_amd_set_wire_form(poporon_t *pprn, const uint8_t to_code[256], const uint8_t to_wire[256],
+                               const uint8_t *xor_seq, size_t xor_len);
+bool poporon_amd_set_wire_form_ccsds(poporon_t *pprn, bool dual_basis, bool randomizer);
+bool poporon_amd_get_wire_form(const poporon_t *pprn, uint8_t to_code[256], uint8_t to_wire[256],
+                               uint8_t *xor_seq /* xor_cap bytes, may be NULL */, size_t xor_cap, size_t *xor_len);
+
 /* ---- decode reports: where the errors were -----------------------------------
  * poporon_decode_batch_report_device takes poporon_decode_batch_device's
  * arguments and three more arrays, poporon_decode_interleaved_report_device
@@ -350,10 +411,12 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
  * the one-codeword-per-wave decoder (rs_wave_k, syndromes included).
  * LDPC handles: 12 = encode (ldpc_encode_k), 13 = decode (ldpc_decode_k),
  * 14 = check (ldpc_check_k).
- * The interleaved calls at depth > 1: 15 = frames to staging rows
- * (rs_ilv_gather_k), 16 = rows back to frames (rs_ilv_scatter_k), one launch
- * each per chunk; the codec kernels between them keep their ids, routed by the
- * chunk's codeword count.
+ * The interleaved calls at depth > 1, and at every depth with a wire form set:
+ * 15 = frames to staging rows (rs_ilv_gather_k, rs_ilv_gather_map_k with a
+ * form), 16 = rows back to frames (rs_ilv_scatter_k, rs_ilv_scatter_map_k),
+ * one launch each per chunk; the codec kernels between them keep their ids,
+ * routed by the chunk's codeword count.  Depth 1 without a form records
+ * neither.
  * The report calls: 17 = the snapshot of a chunk's rows (a device copy, or
  * rs_snapshot_k for rows that are not wire rows), 18 = rs_report_k, one each
  * per chunk, around the decode's own ids.  19 = rs_mask_lists_k

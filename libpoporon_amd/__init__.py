@@ -97,6 +97,9 @@ _SIGS = {
     "poporon_decode_interleaved": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                               C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp]),
     "poporon_amd_reserve_interleaved": (C.c_bool, [_vp, C.c_size_t]),
+    "poporon_amd_set_wire_form": (C.c_bool, [_vp, _vp, _vp, _vp, C.c_size_t]),
+    "poporon_amd_set_wire_form_ccsds": (C.c_bool, [_vp, C.c_bool, C.c_bool]),
+    "poporon_amd_get_wire_form": (C.c_bool, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "poporon_decode_batch_report_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                                       _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
                                                       _vp]),
@@ -224,6 +227,50 @@ def _u8(a, copy=False):
     if isinstance(a, (bytes, bytearray, memoryview)):
         a = np.frombuffer(bytes(a), dtype=np.uint8)
     return np.array(a, dtype=np.uint8, copy=True) if copy else np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def ccsds_dual_basis():
+    """(to_code, to_wire) u8[256] each: CCSDS 131.0-B's conventional <-> dual-basis symbol maps,
+    from the definition (numpy, independent of the library's own tables).  Field 0x187, alpha = 2,
+    beta = alpha^117, Tr(a) = a + a^2 + ... + a^128: bit 7-i of to_wire[u] is Tr(u * beta^i)."""
+    exp = np.zeros(255, np.int64)
+    x = 1
+    for i in range(255):
+        exp[i] = x
+        x <<= 1
+        if x & 0x100:
+            x ^= 0x187
+    log = np.zeros(256, np.int64)
+    log[exp] = np.arange(255)
+
+    def mul(a, b):
+        return np.where((a == 0) | (b == 0), 0, exp[(log[a] + log[b]) % 255])
+
+    u = np.arange(256)
+    to_wire = np.zeros(256, np.int64)
+    for i in range(8):
+        p = mul(u, np.full(256, exp[(117 * i) % 255]))
+        tr = np.zeros(256, np.int64)
+        for _ in range(8):
+            tr ^= p
+            p = mul(p, p)
+        assert ((tr == 0) | (tr == 1)).all()
+        to_wire |= tr << (7 - i)
+    to_wire = to_wire.astype(np.uint8)
+    to_code = np.zeros(256, np.uint8)
+    to_code[to_wire] = u
+    return to_code, to_wire
+
+
+def ccsds_randomizer():
+    """u8[255]: CCSDS 131.0-B's pseudo-randomizer, h(x) = x^8 + x^7 + x^5 + x^3 + 1 from the all-ones
+    state, one period, bits packed MSB first."""
+    s = [1] * 8
+    bits = np.zeros(255 * 8, np.uint8)
+    for n in range(bits.size):
+        bits[n] = s[0]
+        s = s[1:] + [s[0] ^ s[3] ^ s[5] ^ s[7]]
+    return np.packbits(bits)
 
 
 class Erasure:
@@ -455,6 +502,33 @@ class Poporon:
                                                         depth, count, *pargs, _buf(ok), _buf(cor)),
                     "poporon_decode_interleaved")
         return ok, cor, d, p
+
+    # ---- wire form of the interleaved calls (include/poporon_amd.h) -------------------
+    def set_wire_form(self, to_code=None, to_wire=None, xor_seq=None):
+        """Symbol map (u8[256] each, mutually inverse; both or neither) and receive-side XOR
+        sequence (1 .. 65536 bytes) of the *_interleaved* calls; all None clears the form."""
+        maps = [None if t is None else _u8(t) for t in (to_code, to_wire)]
+        if any(t is not None and t.size != 256 for t in maps):
+            raise PoporonError("a symbol map has 256 entries")
+        seq = None if xor_seq is None else _u8(xor_seq).reshape(-1)
+        self._check(self.lib.poporon_amd_set_wire_form(self.h, *(None if t is None else _buf(t) for t in maps),
+                                                       None if seq is None else _buf(seq),
+                                                       0 if seq is None else seq.size),
+                    "poporon_amd_set_wire_form")
+
+    def set_wire_form_ccsds(self, dual_basis=True, randomizer=True):
+        """CCSDS 131.0-B: Berlekamp's dual-basis symbols and / or the 255-byte pseudo-randomizer."""
+        self._check(self.lib.poporon_amd_set_wire_form_ccsds(self.h, bool(dual_basis), bool(randomizer)),
+                    "poporon_amd_set_wire_form_ccsds")
+
+    def wire_form(self):
+        """(to_code u8[256], to_wire u8[256], xor_seq u8[n]) as last set, or None when no form is set."""
+        tc, tw = np.zeros(256, np.uint8), np.zeros(256, np.uint8)
+        seq = np.zeros(65536, np.uint8)
+        n = C.c_size_t(0)
+        if not self.lib.poporon_amd_get_wire_form(self.h, _buf(tc), _buf(tw), _buf(seq), seq.size, C.byref(n)):
+            return None
+        return tc, tw, seq[:n.value].copy()
 
     # ---- decode reports and erasure lists from flag planes (include/poporon_amd.h) ---
     # the report of codeword c: d_err_num[c] changed bytes, their positions (0 .. size-1 message,

@@ -149,6 +149,11 @@ struct GpuCtx {
      * RS_ILV_ROW bytes per codeword allocated; ordered as ilv is */
     uint8_t *rep = nullptr;
     size_t rep_cap = 0;
+    /* the wire form's device image (RS_ILV_WIRE_BYTES, rs_device.h); wire_ok: it
+     * holds the handle's form as last set (ensure_wire) */
+    uint8_t *wire = nullptr;
+    size_t wire_cap = 0;
+    bool wire_ok = false;
     /* Ordering of the workspace across streams: rem_done is recorded on the
      * stream of the last launch that read rem (rem_stream); a call on another
      * stream waits for it before overwriting rem. */
@@ -221,6 +226,11 @@ struct _poporon_t {
     bool nrsplit;   /* ... and large error-mode batches decode on the split kernels (params_nrsplit) */
     size_t ilv_chunk; /* codewords the interleaved calls stage at a time (POPORON_AMD_ILV_CHUNK) */
     size_t rep_chunk; /* codewords the report calls snapshot at a time (POPORON_AMD_REPORT_CHUNK) */
+    /* wire form of the interleaved calls (poporon_amd_set_wire_form), the host copy: wf_set with a
+     * map (wf_map; else the tables hold the identity), a sequence (wf_seq not empty) or both */
+    bool wf_set, wf_map;
+    uint8_t wf_code[256], wf_wire[256];
+    std::vector<uint8_t> wf_seq;
     int gen_path;   /* general kernels: 0 by batch size, 1 one codeword per lane (rsg_*), 2 one per wave
                        (rsgw_*); POPORON_AMD_GENERIC=lane|wave */
     RsDevTables host_tab;
@@ -1099,7 +1109,7 @@ static void gpu_release(GpuCtx &g)
 {
     const int dev = g.device;
     const bool any = g.ready || g.stream || g.sstream || g.tab || g.gtab || g.rem || g.ltab || g.lws || g.stage ||
-                     g.hstage || g.zc || g.ilv || g.rep || g.rslot.stream ||
+                     g.hstage || g.zc || g.ilv || g.rep || g.wire || g.rslot.stream ||
                      g.rem_done || g.registered || g.batch_ev ||
                      g.pipe[0].stream || g.pipe[1].stream || g.pipe[2].stream;
     if (!any || dev < 0) {
@@ -1130,6 +1140,7 @@ static void gpu_release(GpuCtx &g)
     (void)hipFree(g.rem);
     (void)hipFree(g.ilv);
     (void)hipFree(g.rep);
+    (void)hipFree(g.wire);
     (void)hipFree(g.ltab);
     (void)hipFree(g.lws);
     (void)hipFree(g.stage);
@@ -2794,13 +2805,42 @@ static bool ilv_args(const poporon_t *h, const char *what, const IlvCall &c)
 
 static bool rep_run(poporon_t *h, const DecodeCall &c, const RepOut &o);
 
+/* The wire form's device image (rs_device.h: to_code, to_wire, the sequence
+ * continued round), the handle's, uploaded by the first call after a form was
+ * set.  No launch reads the old image by then: poporon_amd_set_wire_form has
+ * waited for them. */
+static bool ensure_wire(poporon_t *h)
+{
+    GpuCtx &g = h->gpu;
+    if (!h->wf_set || g.wire_ok)
+        return true;
+    const size_t xlen = h->wf_seq.size(), bytes = RS_ILV_WIRE_BYTES(xlen);
+    if (g.wire_cap < bytes) {
+        HIP_OK(hipFree(g.wire));
+        g.wire = nullptr;
+        g.wire_cap = 0;
+        HIP_OK(hipMalloc((void **)&g.wire, bytes));
+        g.wire_cap = bytes;
+    }
+    std::vector<uint8_t> img(bytes);
+    memcpy(img.data(), h->wf_code, 256);
+    memcpy(img.data() + 256, h->wf_wire, 256);
+    for (size_t i = 0; i + 512 < bytes; i++)
+        img[512 + i] = h->wf_seq[i % xlen];
+    HIP_OK(hipMemcpy(g.wire, img.data(), bytes, hipMemcpyHostToDevice));
+    g.wire_ok = true;
+    return true;
+}
+
 /* device pointers; the caller holds the batch scope and the device */
 static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
 {
     GpuCtx &g = h->gpu;
     const uint32_t nr = h->rs->num_roots;
     const size_t cf = ilv_chunk_frames(h, c.depth);
-    const bool staged = c.depth > 1;
+    /* with a wire form every byte changes on its way in and out: depth 1 is staged too */
+    const bool mapped = h->wf_set;
+    const bool staged = c.depth > 1 || mapped;
     const bool report = c.op == ILV_DECODE && c.rep.num;
     if (report && !staged) /* depth 1 is the row layout: the row report */
         return rep_run(h, {.data = c.data, .ds = c.ds, .par = c.par, .ps = c.ps, .size = c.size, .count = c.count,
@@ -2811,12 +2851,20 @@ static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
         return false;
     if (staged && (!ensure_ilv(h, std::min(c.count, cf) * c.depth) || !rem_acquire(g, s)))
         return false;
+    if (mapped && !ensure_wire(h))
+        return false;
+    /* an encode reads the message through to_code and uses no sequence */
+    const uint32_t xlen = c.op == ILV_ENCODE ? 0u : (uint32_t)h->wf_seq.size();
     for (size_t f0 = 0; f0 < c.count; f0 += cf) {
         const size_t n = std::min(cf, c.count - f0), ncw = n * c.depth, c0 = f0 * c.depth;
         uint8_t *fd = c.data + f0 * c.ds, *fp = c.par + f0 * c.ps;
         uint8_t *rd = staged ? g.ilv : fd, *rp = staged ? g.ilv + c.size : fp;
         const size_t rds = staged ? c.size + nr : c.ds, rps = staged ? c.size + nr : c.ps; /* staged: wire rows */
-        if (staged)
+        if (mapped)
+            STAGE(g, POPORON_AMD_KERNEL_ILV_GATHER, s,
+                  rsk_ilv_gather_map(fd, c.ds, fp, c.ps, g.ilv, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
+                                     c.op != ILV_ENCODE, g.wire, xlen, s));
+        else if (staged)
             STAGE(g, POPORON_AMD_KERNEL_ILV_GATHER, s,
                   rsk_ilv_gather(fd, c.ds, fp, c.ps, g.ilv, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
                                  c.op != ILV_ENCODE, s));
@@ -2838,7 +2886,11 @@ static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
         } else if (!launch_check(h, rd, rds, rp, rps, c.size, ncw, c.dirty + c0, s)) {
             return false;
         }
-        if (staged && c.op != ILV_CHECK)
+        if (mapped && c.op != ILV_CHECK)
+            STAGE(g, POPORON_AMD_KERNEL_ILV_SCATTER, s,
+                  rsk_ilv_scatter_map(g.ilv, fd, c.ds, fp, c.ps, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
+                                      c.op == ILV_DECODE, g.wire, s));
+        else if (staged && c.op != ILV_CHECK)
             STAGE(g, POPORON_AMD_KERNEL_ILV_SCATTER, s,
                   rsk_ilv_scatter(g.ilv, fd, c.ds, fp, c.ps, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
                                   c.op == ILV_DECODE, s));
@@ -2899,7 +2951,7 @@ EXPORT bool poporon_amd_reserve_interleaved(poporon_t *h, size_t max_codewords)
     DeviceGuard dg(h->gpu.device);
     /* a chunk is ilv_chunk codewords at most, or one frame where that is more */
     const size_t n = std::min(max_codewords, std::max(h->ilv_chunk, (size_t)RS_ILV_MAX_DEPTH));
-    return ensure_ilv(h, n) && ensure_rem(h, n);
+    return ensure_ilv(h, n) && ensure_rem(h, n) && ensure_wire(h);
 }
 
 /* Host forms: chunks of frames through one pinned slot and the device form,
@@ -2979,6 +3031,133 @@ EXPORT bool poporon_decode_interleaved(poporon_t *h, uint8_t *data, size_t data_
     const IlvCall c = {ILV_DECODE, data,      data_stride,      parity, parity_stride, size,      depth,
                        count,      positions, positions_stride, counts, ok,            corrected, nullptr};
     return ilv_host(h, "poporon_decode_interleaved", c);
+}
+
+/* ------------------------------------------------------------------------ */
+/* wire form of the interleaved calls: symbol map and receive-side sequence  */
+/* ------------------------------------------------------------------------ */
+
+static bool wire_handle(const poporon_t *h, const char *what)
+{
+    if (!h)
+        return fail("%s: NULL handle", what);
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("%s serves RS handles", what);
+    if (h->rs->gf->symbol_size != 8)
+        return fail("%s: a wire form maps bytes; the handle's symbol_size is %u, not 8", what,
+                    (unsigned)h->rs->gf->symbol_size);
+    return true;
+}
+
+EXPORT bool poporon_amd_set_wire_form(poporon_t *h, const uint8_t to_code[256], const uint8_t to_wire[256],
+                                      const uint8_t *xor_seq, size_t xor_len)
+{
+    const char *what = "poporon_amd_set_wire_form";
+    if (!wire_handle(h, what))
+        return false;
+    if (!to_code != !to_wire)
+        return fail("%s: to_code and to_wire are both given or both NULL", what);
+    if (!xor_seq != !xor_len)
+        return fail("%s: xor_seq and xor_len are both given or NULL and 0", what);
+    if (xor_len > RS_ILV_XOR_MAX)
+        return fail("%s: xor_len %zu outside [1, %u]", what, xor_len, (unsigned)RS_ILV_XOR_MAX);
+    if (to_code)
+        for (unsigned v = 0; v < 256; v++)
+            if (to_wire[to_code[v]] != v)
+                return fail("%s: to_wire[to_code[%u]] = %u: the maps are not mutually inverse", what, v,
+                            (unsigned)to_wire[to_code[v]]);
+    /* launches already enqueued keep the form they were given: the device image
+     * is replaced (by the next call's ensure_wire) only after they have run */
+    GpuCtx &g = h->gpu;
+    if (g.ready && g.wire) {
+        DeviceGuard dg(g.device);
+        if (g.rem_pending)
+            HIP_OK(hipEventSynchronize(g.rem_done));
+        g.rem_pending = false;
+    }
+    g.wire_ok = false;
+    h->wf_map = to_code != nullptr;
+    for (unsigned v = 0; v < 256; v++) {
+        h->wf_code[v] = to_code ? to_code[v] : (uint8_t)v;
+        h->wf_wire[v] = to_wire ? to_wire[v] : (uint8_t)v;
+    }
+    h->wf_seq.assign(xor_seq, xor_seq + xor_len);
+    h->wf_set = h->wf_map || xor_len;
+    return true;
+}
+
+/* GF(2^8) by 0x187 with alpha = 2: CCSDS 131.0-B's field, whatever the handle's */
+static uint8_t ccsds_mul(uint8_t a, uint8_t b)
+{
+    unsigned r = 0, x = a;
+    for (unsigned i = 0; i < 8; i++, x = (x << 1) ^ ((x & 0x80u) ? 0x187u : 0u))
+        if (b >> i & 1u)
+            r ^= x;
+    return (uint8_t)r;
+}
+
+EXPORT bool poporon_amd_set_wire_form_ccsds(poporon_t *h, bool dual_basis, bool randomizer)
+{
+    if (!wire_handle(h, "poporon_amd_set_wire_form_ccsds"))
+        return false;
+    uint8_t code[256], wire[256], seq[255];
+    if (dual_basis) {
+        /* bit 7-i of to_wire[u] = Tr(u beta^i), beta = alpha^117, Tr(a) = a + a^2 + ... + a^128 */
+        uint8_t beta = 1, bi[8];
+        for (unsigned i = 0; i < 117; i++)
+            beta = ccsds_mul(beta, 2);
+        bi[0] = 1;
+        for (unsigned i = 1; i < 8; i++)
+            bi[i] = ccsds_mul(bi[i - 1], beta);
+        for (unsigned u = 0; u < 256; u++) {
+            unsigned z = 0;
+            for (unsigned i = 0; i < 8; i++) {
+                uint8_t p = ccsds_mul((uint8_t)u, bi[i]), tr = 0;
+                for (unsigned k = 0; k < 8; k++, p = ccsds_mul(p, p))
+                    tr ^= p;
+                z |= (unsigned)(tr & 1u) << (7 - i);
+            }
+            wire[u] = (uint8_t)z;
+        }
+        for (unsigned u = 0; u < 256; u++)
+            code[wire[u]] = (uint8_t)u;
+    }
+    if (randomizer) {
+        /* h(x) = x^8 + x^7 + x^5 + x^3 + 1 from the all-ones state: out s0, in s0^s3^s5^s7; MSB first */
+        unsigned s = 0xFFu; /* bit k: s_k */
+        for (unsigned n = 0; n < 255; n++) {
+            unsigned b = 0;
+            for (unsigned k = 0; k < 8; k++) {
+                b = b << 1 | (s & 1u);
+                const unsigned in = (s ^ s >> 3 ^ s >> 5 ^ s >> 7) & 1u;
+                s = s >> 1 | in << 7;
+            }
+            seq[n] = (uint8_t)b;
+        }
+    }
+    return poporon_amd_set_wire_form(h, dual_basis ? code : nullptr, dual_basis ? wire : nullptr,
+                                     randomizer ? seq : nullptr, randomizer ? 255 : 0);
+}
+
+EXPORT bool poporon_amd_get_wire_form(const poporon_t *h, uint8_t to_code[256], uint8_t to_wire[256],
+                                      uint8_t *xor_seq, size_t xor_cap, size_t *xor_len)
+{
+    const char *what = "poporon_amd_get_wire_form";
+    if (!wire_handle(h, what))
+        return false;
+    if (!h->wf_set)
+        return fail("%s: no wire form is set", what);
+    if (xor_len)
+        *xor_len = h->wf_seq.size();
+    if (xor_seq && xor_cap < h->wf_seq.size())
+        return fail("%s: the sequence has %zu bytes, xor_cap is %zu", what, h->wf_seq.size(), xor_cap);
+    if (to_code)
+        memcpy(to_code, h->wf_code, 256);
+    if (to_wire)
+        memcpy(to_wire, h->wf_wire, 256);
+    if (xor_seq && !h->wf_seq.empty())
+        memcpy(xor_seq, h->wf_seq.data(), h->wf_seq.size());
+    return true;
 }
 
 /* ------------------------------------------------------------------------ */

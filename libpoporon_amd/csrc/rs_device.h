@@ -419,6 +419,21 @@ hipError_t rsk_ilv_gather(const uint8_t *data, size_t dstride, const uint8_t *pa
 hipError_t rsk_ilv_scatter(const uint8_t *rows, uint8_t *data, size_t dstride, uint8_t *parity, size_t pstride,
                            uint32_t size, uint32_t nr, uint32_t depth, size_t nframes, bool with_data,
                            hipStream_t stream);
+/* The same with a wire form (poporon_amd_set_wire_form): frame bytes are
+ * to_code[wire ^ seq[b mod xlen]] on the way in (b: the byte's offset in the
+ * wire block, the parity region's first byte at size*depth) and to_wire[code]
+ * on the way out.  `wire` is the form's device image, RS_ILV_WIRE_BYTES(xlen)
+ * bytes on a 4-byte boundary: to_code[256], to_wire[256], then the sequence
+ * continued round, seq[i mod xlen] for i < xlen + 20 (xlen 0: no sequence). */
+#define RS_ILV_XOR_MAX 65536u
+#define RS_ILV_WIRE_SEQ(xlen) ((size_t)(xlen) ? ((size_t)(xlen) + 23u) & ~(size_t)3 : (size_t)0)
+#define RS_ILV_WIRE_BYTES(xlen) ((size_t)512 + RS_ILV_WIRE_SEQ(xlen))
+hipError_t rsk_ilv_gather_map(const uint8_t *data, size_t dstride, const uint8_t *parity, size_t pstride,
+                              uint8_t *rows, uint32_t size, uint32_t nr, uint32_t depth, size_t nframes,
+                              bool with_parity, const uint8_t *wire, uint32_t xlen, hipStream_t stream);
+hipError_t rsk_ilv_scatter_map(const uint8_t *rows, uint8_t *data, size_t dstride, uint8_t *parity, size_t pstride,
+                               uint32_t size, uint32_t nr, uint32_t depth, size_t nframes, bool with_data,
+                               const uint8_t *wire, hipStream_t stream);
 
 /*
  * Reports and erasure lists (rs_report.hip): the sparse non-zero bytes of a

@@ -37,6 +37,17 @@
  * dwords each, so they meet on no bank; the row pitch W is the padding (an
  * odd W never puts rows 16 apart on one bank; a shortened code whose W is a
  * multiple of 8 does, up to 4-way at D = 64).
+ *
+ * Wire form (poporon_amd_set_wire_form): the mapped variants
+ * rs_ilv_gather_map_k / rs_ilv_scatter_map_k are the same bodies compiled with
+ * MAP = true.  The byte step on the frame side then goes through a 256-byte
+ * table held in LDS beside the tile (to_code on the way in, to_wire on the way
+ * out), and the gather XORs each 16-byte frame slot with the 16 bytes of the
+ * receive sequence that fall on it before the lookup.  The sequence comes from
+ * a device image ext[i] = seq[i mod xlen], i < xlen + 20: a slot whose first
+ * byte has block offset b takes ext[b mod xlen .. + 16), one division per slot
+ * and five aligned dword loads, shifted into place.  With MAP = false the
+ * bodies pass an empty struct around and nothing of this is compiled in.
  */
 #include "rs_device.h"
 
@@ -76,12 +87,41 @@ static __device__ __forceinline__ uint4 ilv_load16(const uint8_t *p, int32_t o0,
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+/* what the mapped variants add: the LDS table, the sequence image (xlen 0:
+ * none) and the block offset of the region's first byte; nothing without a
+ * form, so that the plain kernels pass nothing */
+template <bool MAP> struct IlvWire {
+};
+template <> struct IlvWire<true> {
+    const uint8_t *lut;
+    const uint32_t *ext;
+    uint32_t xlen, boff;
+};
+
+/* the 16 sequence bytes on the slot whose byte 0 has block offset boff + o0
+ * (o0 >= -15: the head slot starts before the region) */
+static __device__ __forceinline__ uint4 ilv_seq16(const IlvWire<true> &wf, int32_t o0)
+{
+    const uint32_t ph = (uint32_t)((int32_t)(wf.boff + 16u * wf.xlen) + o0) % wf.xlen;
+    const uint32_t *e = wf.ext + (ph >> 2);
+    const uint32_t sh = 8u * (ph & 3u);
+    uint32_t d[5], w[4];
+#pragma unroll
+    for (uint32_t i = 0; i < 5u; i++)
+        d[i] = e[i];
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; i++)
+        w[i] = (uint32_t)((((uint64_t)d[i + 1u] << 32) | d[i]) >> sh);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 /* frames -> LDS rows (row pitch `pitch` bytes): region of nsym symbols per
  * codeword (nsym * depth bytes per frame, `stride` apart), LDS columns col0 ..
  * col0 + nsym.  A lane loads RS_ILV_BATCH slots before it spreads the first:
  * the loads' latency is paid once per batch, not once per slot. */
+template <bool MAP>
 static __device__ void ilv_region_in(uint8_t *lds, uint32_t pitch, const uint8_t *reg, size_t stride, uint32_t nsym,
-                                     uint32_t depth, uint32_t col0, uint32_t f0, uint32_t fc)
+                                     uint32_t depth, uint32_t col0, uint32_t f0, uint32_t fc, IlvWire<MAP> wf)
 {
     const uint32_t len = nsym * depth;
     const uint32_t nq = len / 16u + 2u; /* slots a region can touch at the worst alignment */
@@ -96,10 +136,17 @@ static __device__ void ilv_region_in(uint8_t *lds, uint32_t pitch, const uint8_t
             if (idx < fc * nq) {
                 fi[u] = idx / nq;
                 const uint8_t *p = reg + (size_t)(f0 + fi[u]) * stride;
-                if (ilv_slot(p, len, idx - fi[u] * nq, o0[u], kb[u], ke[u]))
+                if (ilv_slot(p, len, idx - fi[u] * nq, o0[u], kb[u], ke[u])) {
                     v[u] = ilv_load16(p, o0[u], kb[u], ke[u]);
-                else
+                    if constexpr (MAP) {
+                        if (wf.xlen) {
+                            const uint4 x = ilv_seq16(wf, o0[u]);
+                            v[u] = make_uint4(v[u].x ^ x.x, v[u].y ^ x.y, v[u].z ^ x.z, v[u].w ^ x.w);
+                        }
+                    }
+                } else {
                     kb[u] = ke[u] = 0u;
+                }
             }
         }
 #pragma unroll
@@ -113,7 +160,10 @@ static __device__ void ilv_region_in(uint8_t *lds, uint32_t pitch, const uint8_t
 #pragma unroll
             for (uint32_t k = 0; k < 16u; k++) {
                 if (k >= kb[u] && k < ke[u]) {
-                    lds[(r0 + i) * pitch + col0 + j] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
+                    uint8_t b = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
+                    if constexpr (MAP)
+                        b = wf.lut[b];
+                    lds[(r0 + i) * pitch + col0 + j] = b;
                     if (++i == depth) {
                         i = 0u;
                         j++;
@@ -125,8 +175,9 @@ static __device__ void ilv_region_in(uint8_t *lds, uint32_t pitch, const uint8_t
 }
 
 /* LDS rows -> frames, the same walk */
+template <bool MAP>
 static __device__ void ilv_region_out(const uint8_t *lds, uint32_t pitch, uint8_t *reg, size_t stride, uint32_t nsym,
-                                      uint32_t depth, uint32_t col0, uint32_t f0, uint32_t fc)
+                                      uint32_t depth, uint32_t col0, uint32_t f0, uint32_t fc, IlvWire<MAP> wf)
 {
     const uint32_t len = nsym * depth;
     const uint32_t nq = len / 16u + 2u;
@@ -144,7 +195,10 @@ static __device__ void ilv_region_out(const uint8_t *lds, uint32_t pitch, uint8_
 #pragma unroll
         for (uint32_t k = 0; k < 16u; k++) {
             if (k >= kb && k < ke) {
-                w[k >> 2] |= (uint32_t)lds[(r0 + i) * pitch + col0 + j] << (8u * (k & 3u));
+                if constexpr (MAP)
+                    w[k >> 2] |= (uint32_t)wf.lut[lds[(r0 + i) * pitch + col0 + j]] << (8u * (k & 3u));
+                else
+                    w[k >> 2] |= (uint32_t)lds[(r0 + i) * pitch + col0 + j] << (8u * (k & 3u));
                 if (++i == depth) {
                     i = 0u;
                     j++;
@@ -172,9 +226,24 @@ struct RsIlvArgs {
     uint32_t both;          /* gather: the parity region too; scatter: the message region too */
 };
 
-__global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_gather_k(RsIlvArgs a)
+/* the mapped variants' arguments: the handle's device image, to_code at byte
+ * 0, to_wire at byte 256, the sequence image from byte 512 (xlen 0: none) */
+struct RsIlvMapArgs {
+    RsIlvArgs a;
+    const uint8_t *wire;
+    uint32_t xlen;
+};
+
+/* 256 table bytes from global memory into LDS, a dword per lane */
+static __device__ __forceinline__ void ilv_lut_in(uint32_t *lut, const uint8_t *tab)
 {
-    __shared__ uint4 lds128[RS_ILV_LDS / 16];
+    if (threadIdx.x < 64u)
+        lut[threadIdx.x] = reinterpret_cast<const uint32_t *>(tab)[threadIdx.x];
+}
+
+template <bool MAP>
+static __device__ __forceinline__ void ilv_gather_body(uint4 *lds128, const RsIlvArgs &a, IlvWire<MAP> wf)
+{
     const uint32_t f0 = blockIdx.x * a.tile;
     if (f0 >= a.nframes)
         return;
@@ -183,9 +252,11 @@ __global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_gather_k(RsIlvArgs a)
     uint8_t *run = a.rows + (size_t)f0 * a.depth * w; /* the tile's rows */
     const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(run) & 15u);
     uint8_t *lds = reinterpret_cast<uint8_t *>(lds128) + head;
-    ilv_region_in(lds, w, a.data, a.dstride, a.size, a.depth, 0u, f0, fc);
+    ilv_region_in<MAP>(lds, w, a.data, a.dstride, a.size, a.depth, 0u, f0, fc, wf);
+    if constexpr (MAP)
+        wf.boff = a.size * a.depth; /* wire-block order wherever the parity region lies */
     if (a.both)
-        ilv_region_in(lds, w, a.parity, a.pstride, a.nr, a.depth, a.size, f0, fc);
+        ilv_region_in<MAP>(lds, w, a.parity, a.pstride, a.nr, a.depth, a.size, f0, fc, wf);
     __syncthreads();
     /* rows out (without the parity region its columns carry whatever LDS held:
      * they are the rows' own bytes, which the encode then writes) */
@@ -204,9 +275,26 @@ __global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_gather_k(RsIlvArgs a)
     }
 }
 
-__global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_scatter_k(RsIlvArgs a)
+__global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_gather_k(RsIlvArgs a)
 {
     __shared__ uint4 lds128[RS_ILV_LDS / 16];
+    ilv_gather_body<false>(lds128, a, IlvWire<false>{});
+}
+
+__global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_gather_map_k(RsIlvMapArgs m)
+{
+    __shared__ uint4 lds128[RS_ILV_LDS / 16];
+    __shared__ uint32_t lut[64];
+    ilv_lut_in(lut, m.wire);
+    __syncthreads();
+    ilv_gather_body<true>(lds128, m.a,
+                          IlvWire<true>{reinterpret_cast<const uint8_t *>(lut),
+                                        reinterpret_cast<const uint32_t *>(m.wire + 512), m.xlen, 0u});
+}
+
+template <bool MAP>
+static __device__ __forceinline__ void ilv_scatter_body(uint4 *lds128, const RsIlvArgs &a, IlvWire<MAP> wf)
+{
     const uint32_t f0 = blockIdx.x * a.tile;
     if (f0 >= a.nframes)
         return;
@@ -253,8 +341,23 @@ __global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_scatter_k(RsIlvArgs a)
     }
     __syncthreads();
     if (a.both)
-        ilv_region_out(lds, w, a.data, a.dstride, a.size, a.depth, 0u, f0, fc);
-    ilv_region_out(lds, w, a.parity, a.pstride, a.nr, a.depth, a.size, f0, fc);
+        ilv_region_out<MAP>(lds, w, a.data, a.dstride, a.size, a.depth, 0u, f0, fc, wf);
+    ilv_region_out<MAP>(lds, w, a.parity, a.pstride, a.nr, a.depth, a.size, f0, fc, wf);
+}
+
+__global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_scatter_k(RsIlvArgs a)
+{
+    __shared__ uint4 lds128[RS_ILV_LDS / 16];
+    ilv_scatter_body<false>(lds128, a, IlvWire<false>{});
+}
+
+/* the table is read after the body's barrier between rows in and frames out */
+__global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_scatter_map_k(RsIlvMapArgs m)
+{
+    __shared__ uint4 lds128[RS_ILV_LDS / 16];
+    __shared__ uint32_t lut[64];
+    ilv_lut_in(lut, m.wire + 256);
+    ilv_scatter_body<true>(lds128, m.a, IlvWire<true>{reinterpret_cast<const uint8_t *>(lut), nullptr, 0u, 0u});
 }
 
 /* whole frames per workgroup for a code of w = size + nr symbols at `depth`:
@@ -269,7 +372,8 @@ static bool ilv_tile(uint32_t w, uint32_t depth, uint32_t &tile)
 }
 
 static hipError_t ilv_launch(bool gather, uint8_t *data, size_t dstride, uint8_t *parity, size_t pstride, uint8_t *rows,
-                             uint32_t size, uint32_t nr, uint32_t depth, size_t nframes, bool both, hipStream_t stream)
+                             uint32_t size, uint32_t nr, uint32_t depth, size_t nframes, bool both,
+                             const uint8_t *wire, uint32_t xlen, hipStream_t stream)
 {
     RsIlvArgs a;
     a.data = data;
@@ -287,10 +391,17 @@ static hipError_t ilv_launch(bool gather, uint8_t *data, size_t dstride, uint8_t
         return hipSuccess;
     a.nframes = (uint32_t)nframes;
     const uint32_t grid = (a.nframes + a.tile - 1u) / a.tile;
-    if (gather)
+    if (wire) {
+        const RsIlvMapArgs m = {a, wire, xlen};
+        if (gather)
+            RS_LAUNCH(rs_ilv_gather_map_k, dim3(grid), dim3(RS_ILV_THREADS), 0, stream, m);
+        else
+            RS_LAUNCH(rs_ilv_scatter_map_k, dim3(grid), dim3(RS_ILV_THREADS), 0, stream, m);
+    } else if (gather) {
         RS_LAUNCH(rs_ilv_gather_k, dim3(grid), dim3(RS_ILV_THREADS), 0, stream, a);
-    else
+    } else {
         RS_LAUNCH(rs_ilv_scatter_k, dim3(grid), dim3(RS_ILV_THREADS), 0, stream, a);
+    }
     return hipGetLastError();
 }
 
@@ -299,7 +410,7 @@ extern "C" hipError_t rsk_ilv_gather(const uint8_t *data, size_t dstride, const 
                                      bool with_parity, hipStream_t stream)
 {
     return ilv_launch(true, const_cast<uint8_t *>(data), dstride, const_cast<uint8_t *>(parity), pstride, rows, size,
-                      nr, depth, nframes, with_parity, stream);
+                      nr, depth, nframes, with_parity, nullptr, 0u, stream);
 }
 
 extern "C" hipError_t rsk_ilv_scatter(const uint8_t *rows, uint8_t *data, size_t dstride, uint8_t *parity,
@@ -307,5 +418,27 @@ extern "C" hipError_t rsk_ilv_scatter(const uint8_t *rows, uint8_t *data, size_t
                                       bool with_data, hipStream_t stream)
 {
     return ilv_launch(false, data, dstride, parity, pstride, const_cast<uint8_t *>(rows), size, nr, depth, nframes,
-                      with_data, stream);
+                      with_data, nullptr, 0u, stream);
+}
+
+/* the mapped variants; `wire` is RS_ILV_WIRE_BYTES(xlen) bytes of device memory
+ * (rs_device.h), xlen 0 for no sequence (an encode passes 0) */
+extern "C" hipError_t rsk_ilv_gather_map(const uint8_t *data, size_t dstride, const uint8_t *parity, size_t pstride,
+                                         uint8_t *rows, uint32_t size, uint32_t nr, uint32_t depth, size_t nframes,
+                                         bool with_parity, const uint8_t *wire, uint32_t xlen, hipStream_t stream)
+{
+    if (!wire || xlen > RS_ILV_XOR_MAX)
+        return hipErrorInvalidValue;
+    return ilv_launch(true, const_cast<uint8_t *>(data), dstride, const_cast<uint8_t *>(parity), pstride, rows, size,
+                      nr, depth, nframes, with_parity, wire, xlen, stream);
+}
+
+extern "C" hipError_t rsk_ilv_scatter_map(const uint8_t *rows, uint8_t *data, size_t dstride, uint8_t *parity,
+                                          size_t pstride, uint32_t size, uint32_t nr, uint32_t depth, size_t nframes,
+                                          bool with_data, const uint8_t *wire, hipStream_t stream)
+{
+    if (!wire)
+        return hipErrorInvalidValue;
+    return ilv_launch(false, data, dstride, parity, pstride, const_cast<uint8_t *>(rows), size, nr, depth, nframes,
+                      with_data, wire, 0u, stream);
 }

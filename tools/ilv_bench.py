@@ -6,7 +6,14 @@ to the same codewords as rows through poporon_*_batch_device and to a
 hipMemcpyAsync device-to-device copy of the same byte count, all from one
 process with the legs alternating inside every step.
 
-    python tools/ilv_bench.py [--steps 10] [--warmup 3] [--batch 1048576]
+    python tools/ilv_bench.py [--steps 10] [--warmup 3] [--batch 1048576] [--wire-form] [--append FILE]
+
+--wire-form adds two legs per depth, alternating with the others: the same
+frames in CCSDS wire form (dual-basis symbols, randomized) decoded by a handle
+with poporon_amd_set_wire_form_ccsds set ("wire_decode"), and the caller-side
+equivalent the wire form replaces ("caller_decode"): torch XOR with the
+sequence and a table gather over the block, the plain interleaved decode, and
+a table gather back.  --append FILE appends the per-depth lines to FILE.
 
 Per depth one JSON line: wall time of call + synchronise (median, min, max
 over the steps, us); per-kernel time per call from the library's events
@@ -72,6 +79,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1 << 20)
+    ap.add_argument("--wire-form", action="store_true")
+    ap.add_argument("--append", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     hip = hip_runtime()
@@ -87,6 +96,12 @@ def main():
     torch.cuda.synchronize()
     hi.reserve_interleaved(n0)
     hr.reserve(n0)
+    if a.wire_form:
+        hw = P.Poporon.default(device=0)  # interleaved calls with the CCSDS wire form
+        hw.set_wire_form_ccsds(True, True)
+        hw.reserve_interleaved(n0)
+        to_code, to_wire = (torch.from_numpy(t).to(dev) for t in P.ccsds_dual_basis())
+        rand = torch.from_numpy(P.ccsds_randomizer()).to(dev)
     result = {"workload": f"RS(255,223), {n0} codewords, {NERR} errors each", "steps": a.steps, "depths": {}}
     for depth in (1, 4, 5, 8):
         frames = n0 // depth
@@ -96,7 +111,7 @@ def main():
         f_clean, f_bad = to_frames(clean), to_frames(bad)
         fw, rw = f_bad.clone(), bad[:n].clone()
         cp = torch.empty_like(fw)
-        ok = torch.zeros((2, n), dtype=torch.uint8, device=dev)
+        ok = torch.zeros((4, n), dtype=torch.uint8, device=dev)
         fp, rp = fw.data_ptr(), rw.data_ptr()
         legs = {
             "ilv_decode": lambda: hi.decode_interleaved_device(fp, fb, fp + K * depth, fb, K, depth, frames,
@@ -106,17 +121,40 @@ def main():
             "row_encode": lambda: hr.encode_batch_device(rp, N, rp + K, N, K, n, s),
             "memcpy_d2d": lambda: hip.hipMemcpyAsync(cp.data_ptr(), fp, n * N, 3, s),
         }
+        owner = {k: hi if k.startswith("ilv") else hr for k in legs}  # whose kernel timers a leg's call fills
+        if a.wire_form:
+            # the sequence as it falls on one block (a frame tensor is [frames, symbol, codeword])
+            seq = rand[torch.arange(fb, device=dev) % rand.numel()].view(N, depth)
+            w_bad, w_clean = to_wire[f_bad.int()] ^ seq, to_wire[f_clean.int()]  # received; decoded, derandomized
+            ww, cw = w_bad.clone(), w_bad.clone()
+            wp, cwp = ww.data_ptr(), cw.data_ptr()
+
+            def caller_decode():
+                torch.bitwise_xor(cw, seq, out=cw)
+                cw.copy_(to_code[cw.int()])
+                hi.decode_interleaved_device(cwp, fb, cwp + K * depth, fb, K, depth, frames, ok[3].data_ptr(),
+                                             stream=s)
+                cw.copy_(to_wire[cw.int()])
+
+            legs["wire_decode"] = lambda: hw.decode_interleaved_device(wp, fb, wp + K * depth, fb, K, depth, frames,
+                                                                       ok[2].data_ptr(), stream=s)
+            legs["caller_decode"] = caller_decode
+            owner.update(wire_decode=hw, caller_decode=hi)
         wall = {k: [] for k in legs}
         kern = {}
         for timing in (False, True):
-            hi.timing(timing)
-            hr.timing(timing)
+            for h in set(owner.values()):
+                h.timing(timing)
             for step in range(a.warmup + a.steps if not timing else a.steps):
                 for name, fn in legs.items():
                     if name == "ilv_decode":
                         fw.copy_(f_bad)
                     elif name == "row_decode":
                         rw.copy_(bad[:n])
+                    elif name == "wire_decode":
+                        ww.copy_(w_bad)
+                    elif name == "caller_decode":
+                        cw.copy_(w_bad)
                     t = timed(fn)
                     if not timing and step >= a.warmup:
                         wall[name].append(t)
@@ -126,12 +164,16 @@ def main():
                         assert torch.equal(rw, clean[:n]) and int(ok[1].sum()) == n
                     elif name == "ilv_encode":
                         assert torch.equal(fw, f_clean)
+                    elif name == "wire_decode":
+                        assert torch.equal(ww, w_clean) and int(ok[2].sum()) == n
+                    elif name == "caller_decode":
+                        assert torch.equal(cw, w_clean) and int(ok[3].sum()) == n
                     if timing and name != "memcpy_d2d":  # this call's kernels; the totals start over
-                        h = hi if name.startswith("ilv") else hr
+                        h = owner[name]
                         kern.setdefault(name, []).append(kernel_ms(h, 1))
                         h.timing(True)
-        hi.timing(False)
-        hr.timing(False)
+        for h in set(owner.values()):
+            h.timing(False)
         kern = {leg: {k: dict(calls[0][k], us_per_call=sorted(c[k]["us_per_call"] for c in calls)[len(calls) // 2])
                       for k in calls[0]} for leg, calls in kern.items()}  # median over the steps
         line = {"depth": depth, "codewords": n, "wall_us": {k: stats(v) for k, v in wall.items()}, "kernels": kern}
@@ -140,14 +182,19 @@ def main():
         # bytes read + written per codeword: decode moves both regions each way, encode the
         # message in and the parity out (row side in dwords: the message's 223 bytes as 224)
         moved = {("ilv_decode", "15"): 2 * N, ("ilv_decode", "16"): 2 * N, ("ilv_encode", "15"): K + K + 1,
-                 ("ilv_encode", "16"): 2 * NR}
+                 ("ilv_encode", "16"): 2 * NR, ("wire_decode", "15"): 2 * N, ("wire_decode", "16"): 2 * N}
         for (leg, kid), b in moved.items():
             if kid in kern.get(leg, {}):
                 rates[f"{leg}_id{kid}_TBps"] = round(n * b / (kern[leg][kid]["us_per_call"] * 1e-6) / 1e12, 3)
         line["rates"] = rates
         result["depths"][depth] = line
         print(json.dumps(line), flush=True)
-        del f_clean, f_bad, fw, rw, cp, ok
+        if a.append:
+            with open(a.append, "a") as f:
+                f.write(json.dumps(line) + "\n")
+        del f_clean, f_bad, fw, rw, cp, ok, legs
+        if a.wire_form:
+            del w_bad, w_clean, ww, cw, seq
     print(json.dumps(result))
 
 
