@@ -327,6 +327,105 @@ bool poporon_amd_erasures_from_mask_device(poporon_t *pprn, const uint8_t *d_mas
                                            size_t depth, size_t count, uint8_t *d_positions, size_t positions_stride,
                                            uint8_t *d_counts, uint8_t *d_over, void *stream);
 
+/* ---- convolutional-interleaver RS streams --------------------------------------
+ * Broadcast and cable links (DVB-S / -T / -C and ISDB-T: RS(204,188), 12
+ * branches of cell 17; ATSC: RS(207,187), 52 branches of cell 4) send their
+ * codewords through a Forney convolutional interleaver: `branches` (I) FIFOs,
+ * branch b of b*cell (b*M) bytes, one byte to each branch in turn.  The
+ * interleaver has memory, but it is a pure index map.  Number the code bytes of
+ * a batch serially, n = c*W + s: c the codeword, s its symbol (message symbols
+ * 0 .. size-1, parity symbols size .. W-1), W = size + num_roots.  Byte n
+ * travels on branch b = (phase + n) mod branches and leaves at stream offset
+ *
+ *     p(n) = n + b * cell * branches.
+ *
+ * A batch of count codewords occupies a span of poporon_amd_conv_span(W, count,
+ * branches, cell) = count*W + (branches-1)*cell*branches bytes, and d_stream
+ * points at span offset 0.  The (branches-1)*cell*branches offsets of the span
+ * that are no p(n) are holes: bytes of the codewords before and after the
+ * batch.  So the calls are stateless.  Successive calls take overlapping
+ * windows of one stream, the next at d_stream + count*W with phase (phase +
+ * count*W) mod branches, and each call touches only its own bytes: calls on
+ * neighbouring windows never write a byte of one another's.
+ *
+ * Limits: 1 <= branches <= 128, 1 <= cell <= 255, phase < branches, 1 <= size
+ * <= 2^symbol_size - 1 - num_roots (as the row decode checks it), strides at
+ * least their regions, any base alignment and any stride.  branches 1 is the
+ * identity: the stream is the wire rows back to back.  count 0 succeeds and
+ * launches nothing.  Every stream offset is computed in size_t.  RS handles
+ * only (BCH and LDPC handles: false with a message).
+ *
+ * Memory touched: nothing outside [0, span) of the stream is read or written,
+ * holes are never written, bytes of a row stride past a region are never
+ * written, const inputs are unchanged.
+ *
+ *  - poporon_amd_conv_interleave_device: rows -> stream, layout only.  Each
+ *    codeword's W bytes are written to their p(n); d_parity NULL: the parity
+ *    offsets keep their contents.
+ *  - poporon_amd_conv_deinterleave_device: the inverse; d_parity NULL: the
+ *    parity symbols are not delivered.  A stream of per-symbol flag bytes goes
+ *    through it with d_parity NULL and then to
+ *    poporon_amd_erasures_from_mask_device at depth 1 (mask_stride = data_stride),
+ *    whose lists feed poporon_decode_conv_device.
+ *  - poporon_encode_conv_device: poporon_encode_batch_device on the rows, which
+ *    writes d_parity (required) exactly as that call does, then the interleave.
+ *  - poporon_decode_conv_device: the de-interleave straight into the caller's
+ *    rows, then poporon_decode_batch_device in place there: no staging buffer
+ *    and no extra pass.  Every per-codeword result (bytes, d_ok, d_corrected,
+ *    erasure semantics, quirks) equals the row call's on the de-interleaved
+ *    rows; a failed codeword comes out as received.  d_parity is required.
+ *  - poporon_decode_conv_report_device: the same with the report arrays of
+ *    poporon_decode_batch_report_device on those rows (its chunks and its
+ *    snapshot buffer: poporon_amd_reserve_report).
+ *  - poporon_check_conv_device: d_dirty[c] as poporon_check_batch_device gives
+ *    it.  The stream is const and there are no rows: chunks of at most
+ *    POPORON_AMD_ILV_CHUNK codewords (default 2^20) are gathered into the
+ *    staging rows of the interleaved calls, chunk by chunk on `stream`, each
+ *    chunk its own window (base + c0*W, phase (phase + c0*W) mod branches).
+ *    poporon_amd_reserve_interleaved pre-sizes that staging.
+ *
+ * The layout, encode and decode calls allocate nothing beyond what the row
+ * calls allocate (poporon_amd_reserve covers it).  A wire form set on the
+ * handle is NOT applied by these calls, as it is not applied by the row calls.
+ * DVB's energy dispersal and sync-byte inversion sit outside the RS code and
+ * stay with the caller.
+ *
+ * Kernels (rs_conv.hip): a workgroup moves a tile of poporon_amd_conv_tile(W,
+ * branches, cell) codewords through an LDS image of its stream window; where
+ * that returns 0 the window does not fit the LDS and a plain path without a
+ * tile runs.  POPORON_AMD_CONV_PATH=tile / direct in the environment at
+ * poporon_create forces either (tile on a geometry that does not fit fails the
+ * call with a message).
+ *
+ * There are no host forms: a host encode would have to merge the partly owned
+ * windows at both ends of its span with the caller's stream, so the caller
+ * copies the span to the device and back instead. */
+/* count*row_bytes + (branches-1)*cell*branches; 0 on invalid arguments or overflow.  No GPU. */
+size_t poporon_amd_conv_span(size_t row_bytes, size_t count, size_t branches, size_t cell);
+/* codewords per workgroup of the tile kernels for rows of row_bytes <= 255 bytes; 0: the direct path.  No GPU. */
+size_t poporon_amd_conv_tile(size_t row_bytes, size_t branches, size_t cell);
+bool poporon_amd_conv_interleave_device(poporon_t *pprn, const uint8_t *d_data, size_t data_stride,
+                                        const uint8_t *d_parity, size_t parity_stride, size_t size, size_t count,
+                                        size_t branches, size_t cell, size_t phase, uint8_t *d_stream, void *stream);
+bool poporon_amd_conv_deinterleave_device(poporon_t *pprn, const uint8_t *d_stream, size_t branches, size_t cell,
+                                          size_t phase, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                          size_t parity_stride, size_t size, size_t count, void *stream);
+bool poporon_encode_conv_device(poporon_t *pprn, const uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                size_t parity_stride, size_t size, size_t count, size_t branches, size_t cell,
+                                size_t phase, uint8_t *d_stream, void *stream);
+bool poporon_decode_conv_device(poporon_t *pprn, const uint8_t *d_stream, size_t branches, size_t cell, size_t phase,
+                                uint8_t *d_data, size_t data_stride, uint8_t *d_parity, size_t parity_stride,
+                                size_t size, size_t count, const uint8_t *d_positions, size_t positions_stride,
+                                const uint8_t *d_counts, uint8_t *d_ok, uint8_t *d_corrected, void *stream);
+bool poporon_decode_conv_report_device(poporon_t *pprn, const uint8_t *d_stream, size_t branches, size_t cell,
+                                       size_t phase, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                       size_t parity_stride, size_t size, size_t count, const uint8_t *d_positions,
+                                       size_t positions_stride, const uint8_t *d_counts, uint8_t *d_ok,
+                                       uint8_t *d_corrected, uint8_t *d_err_num, uint8_t *d_err_pos,
+                                       uint8_t *d_err_val, size_t report_stride, void *stream);
+bool poporon_check_conv_device(poporon_t *pprn, const uint8_t *d_stream, size_t branches, size_t cell, size_t phase,
+                               size_t size, size_t count, uint8_t *d_dirty, void *stream);
+
 /* ---- LDPC batches -----------------------------------------------------------
  * Row c has info_bytes (poporon_get_info_size) of data at d_data +
  * c*data_stride and parity_bytes (poporon_get_parity_size) of parity at
@@ -421,6 +520,10 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
  * rs_snapshot_k for rows that are not wire rows), 18 = rs_report_k, one each
  * per chunk, around the decode's own ids.  19 = rs_mask_lists_k
  * (poporon_amd_erasures_from_mask_device).
+ * The convolutional-interleaver calls: 20 = stream to rows (rs_conv_gather_k,
+ * or rs_conv_gather_direct_k on the plain path), 21 = rows to stream
+ * (rs_conv_scatter_k, rs_conv_scatter_direct_k), one launch per layout pass
+ * (the check: one per chunk); the codec kernels keep their ids.
  *
  * Error- and erasure-mode batches of at least 16384 codewords take the split
  * decode; POPORON_AMD_DECODE_PATH=split / single / wave in the environment
@@ -446,6 +549,8 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
 #define POPORON_AMD_KERNEL_SNAPSHOT 17
 #define POPORON_AMD_KERNEL_REPORT 18
 #define POPORON_AMD_KERNEL_MASK_LISTS 19
+#define POPORON_AMD_KERNEL_CONV_GATHER 20
+#define POPORON_AMD_KERNEL_CONV_SCATTER 21
 bool poporon_amd_timing(poporon_t *pprn, int enable);
 bool poporon_amd_timing_read(poporon_t *pprn, int kernel, double *total_ms, uint64_t *launches);
 

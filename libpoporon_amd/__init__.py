@@ -111,6 +111,22 @@ _SIGS = {
     "poporon_amd_reserve_report": (C.c_bool, [_vp, C.c_size_t]),
     "poporon_amd_erasures_from_mask_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                          _vp, C.c_size_t, _vp, _vp, _vp]),
+    "poporon_amd_conv_span": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "poporon_amd_conv_tile": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t]),
+    "poporon_amd_conv_interleave_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                      C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp]),
+    "poporon_amd_conv_deinterleave_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_size_t,
+                                                        _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp]),
+    "poporon_encode_conv_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                              C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp]),
+    "poporon_decode_conv_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp,
+                                              C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp,
+                                              _vp]),
+    "poporon_decode_conv_report_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_size_t,
+                                                     _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp,
+                                                     _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "poporon_check_conv_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                             _vp, _vp]),
     "poporon_rng_create": (_vp, [C.c_int, _vp, C.c_size_t]),
     "poporon_rng_destroy": (None, [_vp]),
     "poporon_rng_next": (C.c_bool, [_vp, _vp, C.c_size_t]),
@@ -143,7 +159,7 @@ _SIGS = {
 }
 
 # kernel ids for poporon_amd_timing_read (include/poporon_amd.h)
-KERNEL_ENCODE, KERNEL_REMAINDER, KERNEL_CORRECT = 0, 1, 2
+KERNEL_ENCODE, KERNEL_REMAINDER, KERNEL_CORRECT, KERNEL_CHECK = 0, 1, 2, 3
 KERNEL_BM, KERNEL_CHIEN, KERNEL_FORNEY, KERNEL_LIST, KERNEL_APPLY, KERNEL_ERASURE, KERNEL_SINGLE = 4, 5, 6, 7, 8, 9, 10
 KERNEL_WAVE = 11
 KERNEL_LDPC_ENCODE, KERNEL_LDPC_DECODE, KERNEL_LDPC_CHECK = 12, 13, 14
@@ -159,6 +175,9 @@ ILV_KERNEL_NAMES = {KERNEL_ILV_GATHER: "rs_ilv_gather_k (frames to rows)",
                     KERNEL_ILV_SCATTER: "rs_ilv_scatter_k (rows to frames)"}
 REPORT_KERNEL_NAMES = {KERNEL_SNAPSHOT: "snapshot (device copy or rs_snapshot_k)", KERNEL_REPORT: "rs_report_k",
                        KERNEL_MASK_LISTS: "rs_mask_lists_k"}
+KERNEL_CONV_GATHER, KERNEL_CONV_SCATTER = 20, 21
+CONV_KERNEL_NAMES = {KERNEL_CONV_GATHER: "rs_conv_gather_k (stream to rows)",
+                     KERNEL_CONV_SCATTER: "rs_conv_scatter_k (rows to stream)"}
 LDPC_KERNEL_NAMES = {KERNEL_LDPC_ENCODE: "ldpc_encode_k", KERNEL_LDPC_DECODE: "ldpc_decode_k",
                      KERNEL_LDPC_CHECK: "ldpc_check_k"}
 
@@ -205,6 +224,22 @@ def header_symbols(include_dir: str = INCLUDE_DIR):
                 if m.group(1) not in names:
                     names.append(m.group(1))
     return names
+
+
+def conv_span(row_bytes: int, count: int, branches: int, cell: int) -> int:
+    """poporon_amd_conv_span: bytes of stream that `count` codewords of row_bytes occupy behind a
+    convolutional interleaver (count*row_bytes + (branches-1)*cell*branches); 0 on invalid arguments."""
+    if min(row_bytes, count, branches, cell) < 0 or max(row_bytes, count, branches, cell) >= 1 << 64:
+        return 0
+    return int(load_library().poporon_amd_conv_span(row_bytes, count, branches, cell))
+
+
+def conv_tile(row_bytes: int, branches: int, cell: int) -> int:
+    """poporon_amd_conv_tile: codewords per workgroup of the convolutional layout kernels' LDS tile;
+    0 where the window does not fit the LDS (the direct path)."""
+    if min(row_bytes, branches, cell) < 0 or max(row_bytes, branches, cell) >= 1 << 64:
+        return 0
+    return int(load_library().poporon_amd_conv_tile(row_bytes, branches, cell))
 
 
 def last_error() -> str:
@@ -582,6 +617,51 @@ class Poporon:
                                                                    d_positions, positions_stride, d_counts, d_over,
                                                                    stream or None),
                     "poporon_amd_erasures_from_mask_device")
+
+    # ---- convolutional-interleaver streams (include/poporon_amd.h) --------------------
+    # byte n = c*(size + num_roots) + s of the batch lies at d_stream + n + ((phase + n) % branches)*cell*branches;
+    # d_stream is offset 0 of the batch's span of conv_span(size + num_roots, count, branches, cell) bytes
+    def conv_interleave_device(self, d_data, data_stride, d_parity, parity_stride, size, count, branches, cell,
+                               phase, d_stream, stream=0):
+        self._check(self.lib.poporon_amd_conv_interleave_device(self.h, d_data, data_stride, d_parity, parity_stride,
+                                                                size, count, branches, cell, phase, d_stream,
+                                                                stream or None),
+                    "poporon_amd_conv_interleave_device")
+
+    def conv_deinterleave_device(self, d_stream, branches, cell, phase, d_data, data_stride, d_parity, parity_stride,
+                                 size, count, stream=0):
+        self._check(self.lib.poporon_amd_conv_deinterleave_device(self.h, d_stream, branches, cell, phase, d_data,
+                                                                  data_stride, d_parity, parity_stride, size, count,
+                                                                  stream or None),
+                    "poporon_amd_conv_deinterleave_device")
+
+    def encode_conv_device(self, d_data, data_stride, d_parity, parity_stride, size, count, branches, cell, phase,
+                           d_stream, stream=0):
+        self._check(self.lib.poporon_encode_conv_device(self.h, d_data, data_stride, d_parity, parity_stride, size,
+                                                        count, branches, cell, phase, d_stream, stream or None),
+                    "poporon_encode_conv_device")
+
+    def decode_conv_device(self, d_stream, branches, cell, phase, d_data, data_stride, d_parity, parity_stride, size,
+                           count, d_ok, d_corrected=None, d_positions=None, positions_stride=0, d_counts=None,
+                           stream=0):
+        self._check(self.lib.poporon_decode_conv_device(self.h, d_stream, branches, cell, phase, d_data, data_stride,
+                                                        d_parity, parity_stride, size, count, d_positions,
+                                                        positions_stride, d_counts, d_ok, d_corrected,
+                                                        stream or None), "poporon_decode_conv_device")
+
+    def decode_conv_report_device(self, d_stream, branches, cell, phase, d_data, data_stride, d_parity, parity_stride,
+                                  size, count, d_ok, d_err_num, d_err_pos, d_err_val, report_stride,
+                                  d_corrected=None, d_positions=None, positions_stride=0, d_counts=None, stream=0):
+        self._check(self.lib.poporon_decode_conv_report_device(self.h, d_stream, branches, cell, phase, d_data,
+                                                               data_stride, d_parity, parity_stride, size, count,
+                                                               d_positions, positions_stride, d_counts, d_ok,
+                                                               d_corrected, d_err_num, d_err_pos, d_err_val,
+                                                               report_stride, stream or None),
+                    "poporon_decode_conv_report_device")
+
+    def check_conv_device(self, d_stream, branches, cell, phase, size, count, d_dirty, stream=0):
+        self._check(self.lib.poporon_check_conv_device(self.h, d_stream, branches, cell, phase, size, count, d_dirty,
+                                                       stream or None), "poporon_check_conv_device")
 
     # ---- in-library kernel timing (HIP events on the launch stream) ---------------
     def timing(self, enable: bool):

@@ -118,7 +118,7 @@ struct _poporon_config_t {
     uint64_t seed;
 };
 
-#define NKERN 20
+#define NKERN 22
 struct TimedLaunch {
     int kernel;
     hipEvent_t a, b;
@@ -226,6 +226,8 @@ struct _poporon_t {
     bool nrsplit;   /* ... and large error-mode batches decode on the split kernels (params_nrsplit) */
     size_t ilv_chunk; /* codewords the interleaved calls stage at a time (POPORON_AMD_ILV_CHUNK) */
     size_t rep_chunk; /* codewords the report calls snapshot at a time (POPORON_AMD_REPORT_CHUNK) */
+    int conv_path;    /* convolutional-interleaver layout kernels: RS_CONV_PATH_AUTO (the LDS tile where the window
+                       * fits), _TILE or _DIRECT (POPORON_AMD_CONV_PATH=tile|direct) */
     /* wire form of the interleaved calls (poporon_amd_set_wire_form), the host copy: wf_set with a
      * map (wf_map; else the tables hold the identity), a sequence (wf_seq not empty) or both */
     bool wf_set, wf_map;
@@ -976,6 +978,13 @@ EXPORT poporon_t *poporon_create(const poporon_config_t *config)
         const char *rc = getenv("POPORON_AMD_REPORT_CHUNK");
         const unsigned long long v = rc ? strtoull(rc, nullptr, 10) : 0ull;
         h->rep_chunk = v ? (size_t)std::min<unsigned long long>(v, REP_CHUNK_MAX) : REP_CHUNK_DEFAULT;
+    }
+    {
+        const char *cp = getenv("POPORON_AMD_CONV_PATH");
+        h->conv_path = !cp                    ? RS_CONV_PATH_AUTO
+                       : !strcmp(cp, "tile")   ? RS_CONV_PATH_TILE
+                       : !strcmp(cp, "direct") ? RS_CONV_PATH_DIRECT
+                                               : RS_CONV_PATH_AUTO;
     }
     if (h->fast)
         build_tables(h);
@@ -3255,6 +3264,220 @@ EXPORT bool poporon_amd_reserve_report(poporon_t *h, size_t max_codewords)
     DeviceGuard dg(h->gpu.device);
     const size_t n = std::min(max_codewords, h->rep_chunk);
     return ensure_rep(h, n) && ensure_rem(h, n);
+}
+
+/* ------------------------------------------------------------------------ */
+/* convolutional-interleaver streams: layout kernels around the row kernels */
+/* ------------------------------------------------------------------------ */
+
+/*
+ * A Forney interleaver of `branches` FIFOs, branch b of b*cell bytes, is an
+ * index map (poporon_amd.h, rs_conv.hip): the calls are stateless, and each
+ * touches only the bytes of its own codewords inside its span.  The codec
+ * kernels are untouched.  A decode gathers the stream straight into the
+ * caller's rows and decodes there; an encode writes the caller's parity rows
+ * and scatters data and parity; a check gathers chunks into the staging rows
+ * of the interleaved calls, each chunk its own window of the stream.
+ */
+struct ConvCall {
+    uint8_t *stream;
+    size_t branches, cell, phase;
+    uint8_t *data;
+    size_t ds;
+    uint8_t *par;
+    size_t ps;
+    size_t size, count;
+    bool need_rows;   /* false: the check, which has no rows */
+    bool need_parity; /* the codec calls */
+};
+
+/* span = count*row_bytes + (branches-1)*cell*branches; false on arguments out of range or overflow */
+static bool conv_span(size_t row_bytes, size_t count, size_t branches, size_t cell, size_t &span)
+{
+    if (row_bytes < 1 || branches < 1 || branches > RS_CONV_MAX_BRANCHES || cell < 1 || cell > RS_CONV_MAX_CELL)
+        return false;
+    const size_t holes = (branches - 1) * cell * branches;
+    if (count > ((size_t)-1 - holes) / row_bytes)
+        return false;
+    span = count * row_bytes + holes;
+    return true;
+}
+
+EXPORT size_t poporon_amd_conv_span(size_t row_bytes, size_t count, size_t branches, size_t cell)
+{
+    size_t span;
+    return conv_span(row_bytes, count, branches, cell, span) ? span : 0;
+}
+
+EXPORT size_t poporon_amd_conv_tile(size_t row_bytes, size_t branches, size_t cell)
+{
+    if (row_bytes > 255 || branches > RS_CONV_MAX_BRANCHES || cell > RS_CONV_MAX_CELL)
+        return 0;
+    return rsk_conv_tile((uint32_t)row_bytes, (uint32_t)branches, (uint32_t)cell);
+}
+
+/* the checks every convolutional entry point makes before it touches the GPU */
+static bool conv_args(const poporon_t *h, const char *what, const ConvCall &c)
+{
+    if (!h)
+        return fail("%s: NULL handle", what);
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("%s serves RS handles", what);
+    if (c.count && (!c.stream || (c.need_rows && !c.data) || (c.need_parity && !c.par)))
+        return fail("%s: NULL argument", what);
+    if (c.branches < 1 || c.branches > RS_CONV_MAX_BRANCHES)
+        return fail("%s: branches %zu outside [1, %u]", what, c.branches, (unsigned)RS_CONV_MAX_BRANCHES);
+    if (c.cell < 1 || c.cell > RS_CONV_MAX_CELL)
+        return fail("%s: cell %zu outside [1, %u]", what, c.cell, (unsigned)RS_CONV_MAX_CELL);
+    if (c.phase >= c.branches)
+        return fail("%s: phase %zu >= branches %zu", what, c.phase, c.branches);
+    if (!check_decode_size(h, c.size))
+        return fail("%s: size %zu outside [1, %u]", what, c.size, (unsigned)kmax(h));
+    const size_t nr = h->rs->num_roots;
+    if (c.need_rows && c.ds < c.size)
+        return fail("%s: data_stride %zu < size %zu", what, c.ds, c.size);
+    if (c.need_rows && c.par && c.ps < nr)
+        return fail("%s: parity_stride %zu < num_roots %zu", what, c.ps, nr);
+    size_t span;
+    if (!conv_span(c.size + nr, c.count, c.branches, c.cell, span))
+        return fail("%s: the span of %zu codewords overflows size_t", what, c.count);
+    if (h->conv_path == RS_CONV_PATH_TILE &&
+        !rsk_conv_tile((uint32_t)(c.size + nr), (uint32_t)c.branches, (uint32_t)c.cell))
+        return fail("%s: POPORON_AMD_CONV_PATH=tile, and the window of %zu branches of cell %zu does not fit the LDS",
+                    what, c.branches, c.cell);
+    return true;
+}
+
+/* one layout pass over codewords [0, count) of the call, rows as given */
+static bool conv_gather(poporon_t *h, const ConvCall &c, hipStream_t s)
+{
+    STAGE(h->gpu, POPORON_AMD_KERNEL_CONV_GATHER, s,
+          rsk_conv_gather(c.stream, (uint32_t)c.branches, (uint32_t)c.cell, (uint32_t)c.phase, c.data, c.ds, c.par,
+                          c.ps, (uint32_t)c.size, h->rs->num_roots, c.count, h->conv_path, s));
+    return true;
+}
+
+static bool conv_scatter(poporon_t *h, const ConvCall &c, hipStream_t s)
+{
+    STAGE(h->gpu, POPORON_AMD_KERNEL_CONV_SCATTER, s,
+          rsk_conv_scatter(c.data, c.ds, c.par, c.ps, (uint32_t)c.size, h->rs->num_roots, c.count,
+                           (uint32_t)c.branches, (uint32_t)c.cell, (uint32_t)c.phase, c.stream, h->conv_path, s));
+    return true;
+}
+
+/* after the argument checks: run(stream) inside the batch scope on the handle's device */
+template <class F> static bool conv_device(poporon_t *h, const ConvCall &c, void *stream, F &&run)
+{
+    if (c.count == 0)
+        return true;
+    if (!batch_enter(h))
+        return false;
+    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
+    DeviceGuard dg(h->gpu.device);
+    return run((hipStream_t)stream);
+}
+
+EXPORT bool poporon_amd_conv_interleave_device(poporon_t *h, const uint8_t *d_data, size_t data_stride,
+                                               const uint8_t *d_parity, size_t parity_stride, size_t size,
+                                               size_t count, size_t branches, size_t cell, size_t phase,
+                                               uint8_t *d_stream, void *stream)
+{
+    const ConvCall c = {d_stream, branches, cell, phase, const_cast<uint8_t *>(d_data), data_stride,
+                        const_cast<uint8_t *>(d_parity), parity_stride, size, count, true, false};
+    return conv_args(h, "poporon_amd_conv_interleave_device", c) &&
+           conv_device(h, c, stream, [&](hipStream_t s) { return conv_scatter(h, c, s); });
+}
+
+EXPORT bool poporon_amd_conv_deinterleave_device(poporon_t *h, const uint8_t *d_stream, size_t branches, size_t cell,
+                                                 size_t phase, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                                 size_t parity_stride, size_t size, size_t count, void *stream)
+{
+    const ConvCall c = {const_cast<uint8_t *>(d_stream), branches, cell, phase, d_data, data_stride, d_parity,
+                        parity_stride, size, count, true, false};
+    return conv_args(h, "poporon_amd_conv_deinterleave_device", c) &&
+           conv_device(h, c, stream, [&](hipStream_t s) { return conv_gather(h, c, s); });
+}
+
+EXPORT bool poporon_encode_conv_device(poporon_t *h, const uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                       size_t parity_stride, size_t size, size_t count, size_t branches, size_t cell,
+                                       size_t phase, uint8_t *d_stream, void *stream)
+{
+    const ConvCall c = {d_stream, branches, cell, phase, const_cast<uint8_t *>(d_data), data_stride, d_parity,
+                        parity_stride, size, count, true, true};
+    return conv_args(h, "poporon_encode_conv_device", c) && conv_device(h, c, stream, [&](hipStream_t s) {
+               return launch_encode(h, c.data, c.ds, c.par, c.ps, c.size, c.count, s) && conv_scatter(h, c, s);
+           });
+}
+
+/* the decode and its report form: rep.num NULL for the plain call */
+static bool conv_decode(poporon_t *h, const char *what, const ConvCall &c, const uint8_t *d_positions,
+                        size_t positions_stride, const uint8_t *d_counts, uint8_t *d_ok, uint8_t *d_corrected,
+                        const RepOut *rep, void *stream)
+{
+    if (!conv_args(h, what, c) ||
+        !decode_row_args(h, what, true, c.data, c.par, c.size, c.count, d_positions, positions_stride, d_counts, d_ok) ||
+        (rep && !rep_args(h, what, c.count, *rep)))
+        return false;
+    return conv_device(h, c, stream, [&](hipStream_t s) {
+        const DecodeCall d = {.data = c.data, .ds = c.ds, .par = c.par, .ps = c.ps, .size = c.size, .count = c.count,
+                              .pos8 = d_positions, .pos_stride = positions_stride, .cnt = d_counts, .ok = d_ok,
+                              .corrected = d_corrected, .s = s};
+        return conv_gather(h, c, s) && (rep ? rep_run(h, d, *rep) : launch_decode(h, d));
+    });
+}
+
+EXPORT bool poporon_decode_conv_device(poporon_t *h, const uint8_t *d_stream, size_t branches, size_t cell,
+                                       size_t phase, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                       size_t parity_stride, size_t size, size_t count, const uint8_t *d_positions,
+                                       size_t positions_stride, const uint8_t *d_counts, uint8_t *d_ok,
+                                       uint8_t *d_corrected, void *stream)
+{
+    const ConvCall c = {const_cast<uint8_t *>(d_stream), branches, cell, phase, d_data, data_stride, d_parity,
+                        parity_stride, size, count, true, true};
+    return conv_decode(h, "poporon_decode_conv_device", c, d_positions, positions_stride, d_counts, d_ok, d_corrected,
+                       nullptr, stream);
+}
+
+EXPORT bool poporon_decode_conv_report_device(poporon_t *h, const uint8_t *d_stream, size_t branches, size_t cell,
+                                              size_t phase, uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
+                                              size_t parity_stride, size_t size, size_t count,
+                                              const uint8_t *d_positions, size_t positions_stride,
+                                              const uint8_t *d_counts, uint8_t *d_ok, uint8_t *d_corrected,
+                                              uint8_t *d_err_num, uint8_t *d_err_pos, uint8_t *d_err_val,
+                                              size_t report_stride, void *stream)
+{
+    const ConvCall c = {const_cast<uint8_t *>(d_stream), branches, cell, phase, d_data, data_stride, d_parity,
+                        parity_stride, size, count, true, true};
+    const RepOut rep = {d_err_num, d_err_pos, d_err_val, report_stride};
+    return conv_decode(h, "poporon_decode_conv_report_device", c, d_positions, positions_stride, d_counts, d_ok,
+                       d_corrected, &rep, stream);
+}
+
+EXPORT bool poporon_check_conv_device(poporon_t *h, const uint8_t *d_stream, size_t branches, size_t cell,
+                                      size_t phase, size_t size, size_t count, uint8_t *d_dirty, void *stream)
+{
+    const char *what = "poporon_check_conv_device";
+    const ConvCall c = {const_cast<uint8_t *>(d_stream), branches, cell, phase, nullptr, 0, nullptr, 0, size, count,
+                        false, false};
+    if (!conv_args(h, what, c))
+        return false;
+    if (count && !d_dirty)
+        return fail("%s: NULL argument", what);
+    return conv_device(h, c, stream, [&](hipStream_t s) {
+        GpuCtx &g = h->gpu;
+        const size_t chunk = h->ilv_chunk, w = size + h->rs->num_roots;
+        if (!ensure_ilv(h, std::min(count, chunk)) || !rem_acquire(g, s))
+            return false;
+        /* chunk k is its own window of the stream: base + c0*W, phase (phase + c0*W) mod branches */
+        for (size_t c0 = 0; c0 < count; c0 += chunk) {
+            const size_t n = std::min(chunk, count - c0);
+            const ConvCall k = {c.stream + c0 * w, branches, cell, (phase + c0 * w % branches) % branches, g.ilv, w,
+                                g.ilv + size, w, size, n, true, true};
+            if (!conv_gather(h, k, s) || !launch_check(h, k.data, w, k.par, w, size, n, d_dirty + c0, s))
+                return false;
+        }
+        return rem_release(g, s);
+    });
 }
 
 /* Host form: chunks of rows through one pinned slot of its own and the device

@@ -436,6 +436,38 @@ hipError_t rsk_ilv_scatter_map(const uint8_t *rows, uint8_t *data, size_t dstrid
                                const uint8_t *wire, hipStream_t stream);
 
 /*
+ * Convolutional-interleaver streams (rs_conv.hip): `branches` FIFOs, branch b
+ * of b*cell bytes.  Byte n = c*(size + nr) + s of the batch (codeword c,
+ * symbol s, message then parity) lies at stream offset n + ((phase + n) mod
+ * branches)*cell*branches; `stream` points at offset 0 of the batch's span of
+ * count*(size + nr) + (branches-1)*cell*branches bytes.
+ *   rsk_conv_gather   stream -> rows (parity NULL: the message regions alone)
+ *   rsk_conv_scatter  rows -> stream (parity NULL: the parity offsets keep
+ *                     their contents); offsets that are no byte of the batch
+ *                     are never written
+ * size + nr <= 255, regions and stream at any alignment, strides >= their
+ * regions.  path: RS_CONV_PATH_AUTO takes the LDS tile kernels where
+ * rsk_conv_tile (codewords per workgroup) is not 0, else the direct kernels;
+ * _TILE fails (hipErrorInvalidConfiguration) where it is 0; _DIRECT takes the
+ * direct kernels, RS_CONV_TILE_MIN codewords per workgroup.
+ */
+#define RS_CONV_MAX_BRANCHES 128u
+#define RS_CONV_MAX_CELL 255u
+#define RS_CONV_LDS 65536u     /* dynamic LDS of a workgroup at the most */
+#define RS_CONV_LDS_SLACK 48u  /* alignment of window and rows within their 16-byte slots */
+#define RS_CONV_TILE_MIN 64u
+#define RS_CONV_PATH_AUTO 0
+#define RS_CONV_PATH_TILE 1
+#define RS_CONV_PATH_DIRECT 2
+uint32_t rsk_conv_tile(uint32_t w, uint32_t branches, uint32_t cell);
+hipError_t rsk_conv_gather(const uint8_t *stream, uint32_t branches, uint32_t cell, uint32_t phase, uint8_t *data,
+                           size_t ds, uint8_t *parity, size_t ps, uint32_t size, uint32_t nr, size_t count, int path,
+                           hipStream_t s);
+hipError_t rsk_conv_scatter(const uint8_t *data, size_t ds, const uint8_t *parity, size_t ps, uint32_t size,
+                            uint32_t nr, size_t count, uint32_t branches, uint32_t cell, uint32_t phase,
+                            uint8_t *stream, int path, hipStream_t s);
+
+/*
  * Reports and erasure lists (rs_report.hip): the sparse non-zero bytes of a
  * codeword-shaped region as an ascending list of at most nr entries per
  * codeword, the slots behind the count 0, bytes nr .. stride never written.
