@@ -426,6 +426,104 @@ bool poporon_decode_conv_report_device(poporon_t *pprn, const uint8_t *d_stream,
 bool poporon_check_conv_device(poporon_t *pprn, const uint8_t *d_stream, size_t branches, size_t cell, size_t phase,
                                size_t size, size_t count, uint8_t *d_dirty, void *stream);
 
+/* ---- plane layout: RS stripes across shards ------------------------------------
+ * Storage keeps a byte-symbol code the other way round from a link: a stripe
+ * has `size` data shards and num_roots parity shards, each a long buffer of its
+ * own, and codeword c is byte c of every shard.  A *plane table* is a HOST array
+ * of W = size + num_roots DEVICE pointers: entries 0 .. size-1 the message
+ * planes, entries size .. W-1 the parity planes; codeword c has symbol j at
+ * planes[j][c]; count is the number of codewords, that is, bytes per plane.
+ * Planes may lie anywhere and at any alignment, and must not overlap.  The
+ * calls are the row calls on the W x count transpose, without the transposes:
+ *
+ *  - poporon_encode_planes_device: every message plane is non-NULL and is not
+ *    written.  Parity plane p receives what poporon_encode_batch_device writes
+ *    to parity[p] of row c.  A NULL parity entry: that plane is not delivered;
+ *    all parity entries NULL fails the call.
+ *  - poporon_decode_planes_device: `lost` is a HOST array of lost_count plane
+ *    indices, strictly ascending, each < W, lost_count <= num_roots (lost
+ *    parity plane p is index size + p); anything else fails the call before
+ *    any launch (an unsorted list would trip quirk Q1).  Lost planes are NEVER
+ *    READ: the row that is decoded holds 0 there.  A lost plane's table entry
+ *    may be NULL: it is neither read nor written.  A surviving plane may not be
+ *    NULL.  lost_count 0 is the errors-only decode.  Otherwise it is the erasure
+ *    decode, and every codeword gets the list lost[0 .. lost_count) followed by
+ *    zeros up to num_roots -- the fill poporon_amd_erasures_from_mask_device
+ *    writes -- and the count lost_count.  d_ok[c], d_corrected[c] (may be NULL)
+ *    and every byte equal poporon_decode_batch_device on that row with that
+ *    list, quirks Q1/Q2 and the corrected_num semantics included.  After the
+ *    call every non-NULL plane holds its symbol of the row as the row call left
+ *    it: a failed codeword's surviving symbols are as received, and its symbols
+ *    in non-NULL lost planes are what the row call left of the 0.
+ *    d_dirty (may be NULL): d_dirty[c] is poporon_check_batch_device's flag on
+ *    the row AFTER the decode.  It exists because of quirk Q2: with one or more
+ *    lost planes and a corrupted surviving symbol the reference pairs the
+ *    magnitudes with the wrong list slots and returns ok = 1 with wrong bytes
+ *    (RS(255,223), 4 lost planes: up to 14 errors; RS(14,10), 1 lost plane: 1
+ *    error), and this library returns exactly that.  d_ok is the reference's
+ *    answer; d_dirty[c] = 1 says that what was written is no codeword.  The
+ *    errors-only decode (a scrub) has no such case.
+ *  - poporon_decode_planes_report_device: the same with the report arrays of
+ *    poporon_decode_batch_report_device on those rows, so d_err_pos is the PLANE
+ *    INDEX: which shard was bad.  A rebuilt non-zero symbol of a lost plane is
+ *    listed with d_err_val = its value (the row held 0).  A failed codeword's
+ *    report is empty.  Needs poporon_amd_reserve_report besides
+ *    poporon_amd_reserve_planes to allocate nothing.
+ *  - poporon_check_planes_device: all planes non-NULL and const; d_dirty[c] as
+ *    poporon_check_batch_device gives it.
+ *  - the _strided forms: one buffer, message plane j at d_data +
+ *    j*data_plane_stride, parity plane p at d_parity + p*parity_plane_stride
+ *    (offsets in size_t; they may pass 2^32).  They fill a table on the host and
+ *    are the table forms from there on, so no entry is NULL.
+ *
+ * Limits: 1 <= size <= 2^symbol_size - 1 - num_roots, as the row decode checks
+ * it.  RS handles only (BCH and LDPC handles: false with a message).  A wire
+ * form set on the handle is NOT applied.  count 0 succeeds and launches nothing
+ * (the table may then be NULL).  Every plane offset is computed in size_t.
+ * Nothing outside [0, count) of a plane is read or written.  The calls are
+ * asynchronous on `stream`; the table and the lost list are consumed before
+ * the call returns (they reach the kernels by value in the launch arguments:
+ * no device table, no copy, no wait).
+ *
+ * How: chunks of at most POPORON_AMD_ILV_CHUNK codewords (default 2^20) run one
+ * after another on `stream`.  Each is gathered into the staging rows of the
+ * interleaved calls (rs_planes.hip), the row kernels run there, routed by the
+ * chunk's count, d_dirty is the check kernel on those rows, and the rows are
+ * scattered back: the parity planes after an encode, every non-NULL plane after
+ * a decode, nothing after a check.  The erasure lists of a rebuild live in a
+ * buffer the handle owns, one chunk's worth on a 16-byte aligned base at a
+ * stride of num_roots rounded up to 16, written once per call.
+ * poporon_amd_reserve_planes sizes that buffer, the staging rows and the
+ * decoders' workspace for min(max_codewords, chunk) codewords, after which
+ * plane calls allocate nothing.  A workgroup moves a tile of
+ * poporon_amd_plane_tile(W) codewords through 32 KiB of LDS at the most; when
+ * every table entry is a multiple of 16 the kernels without a byte path at
+ * the ends of a plane's run are taken.  There are no host forms. */
+/* codewords per workgroup tile of the plane kernels for rows of row_bytes <= 255 bytes: a multiple of 16, at least
+ * 64; 0 for a row_bytes that is no row.  No GPU. */
+size_t poporon_amd_plane_tile(size_t row_bytes);
+bool poporon_amd_reserve_planes(poporon_t *pprn, size_t max_codewords);
+bool poporon_encode_planes_device(poporon_t *pprn, uint8_t *const *planes, size_t size, size_t count, void *stream);
+bool poporon_decode_planes_device(poporon_t *pprn, uint8_t *const *planes, size_t size, size_t count,
+                                  const uint8_t *lost, size_t lost_count, uint8_t *d_ok, uint8_t *d_corrected,
+                                  uint8_t *d_dirty, void *stream);
+bool poporon_decode_planes_report_device(poporon_t *pprn, uint8_t *const *planes, size_t size, size_t count,
+                                         const uint8_t *lost, size_t lost_count, uint8_t *d_ok, uint8_t *d_corrected,
+                                         uint8_t *d_dirty, uint8_t *d_err_num, uint8_t *d_err_pos, uint8_t *d_err_val,
+                                         size_t report_stride, void *stream);
+bool poporon_check_planes_device(poporon_t *pprn, const uint8_t *const *planes, size_t size, size_t count,
+                                 uint8_t *d_dirty, void *stream);
+bool poporon_encode_planes_strided_device(poporon_t *pprn, const uint8_t *d_data, size_t data_plane_stride,
+                                          uint8_t *d_parity, size_t parity_plane_stride, size_t size, size_t count,
+                                          void *stream);
+bool poporon_decode_planes_strided_device(poporon_t *pprn, uint8_t *d_data, size_t data_plane_stride,
+                                          uint8_t *d_parity, size_t parity_plane_stride, size_t size, size_t count,
+                                          const uint8_t *lost, size_t lost_count, uint8_t *d_ok, uint8_t *d_corrected,
+                                          uint8_t *d_dirty, void *stream);
+bool poporon_check_planes_strided_device(poporon_t *pprn, const uint8_t *d_data, size_t data_plane_stride,
+                                         const uint8_t *d_parity, size_t parity_plane_stride, size_t size,
+                                         size_t count, uint8_t *d_dirty, void *stream);
+
 /* ---- LDPC batches -----------------------------------------------------------
  * Row c has info_bytes (poporon_get_info_size) of data at d_data +
  * c*data_stride and parity_bytes (poporon_get_parity_size) of parity at
@@ -524,6 +622,11 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
  * or rs_conv_gather_direct_k on the plain path), 21 = rows to stream
  * (rs_conv_scatter_k, rs_conv_scatter_direct_k), one launch per layout pass
  * (the check: one per chunk); the codec kernels keep their ids.
+ * The plane calls: 22 = planes to staging rows (rs_plane_gather_k; on the
+ * first chunk of a rebuild rs_plane_lists_k runs in the same timed stage),
+ * 23 = rows back to planes (rs_plane_scatter_k), one each per chunk: 22 alone
+ * for a check, 23 only the parity planes for an encode; the codec kernels
+ * between them keep their ids, d_dirty is one more launch of 3.
  *
  * Error- and erasure-mode batches of at least 16384 codewords take the split
  * decode; POPORON_AMD_DECODE_PATH=split / single / wave in the environment
@@ -551,6 +654,8 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
 #define POPORON_AMD_KERNEL_MASK_LISTS 19
 #define POPORON_AMD_KERNEL_CONV_GATHER 20
 #define POPORON_AMD_KERNEL_CONV_SCATTER 21
+/* the plane calls' ids are enumerators: tests/test_conv_cpu.py pins the macro ids above to 22 of them */
+enum { POPORON_AMD_KERNEL_PLANE_GATHER = 22, POPORON_AMD_KERNEL_PLANE_SCATTER = 23 };
 bool poporon_amd_timing(poporon_t *pprn, int enable);
 bool poporon_amd_timing_read(poporon_t *pprn, int kernel, double *total_ms, uint64_t *launches);
 

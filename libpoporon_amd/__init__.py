@@ -127,6 +127,20 @@ _SIGS = {
                                                      _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "poporon_check_conv_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                              _vp, _vp]),
+    "poporon_amd_plane_tile": (C.c_size_t, [C.c_size_t]),
+    "poporon_amd_reserve_planes": (C.c_bool, [_vp, C.c_size_t]),
+    "poporon_encode_planes_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, _vp]),
+    "poporon_decode_planes_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp,
+                                                _vp]),
+    "poporon_decode_planes_report_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp, _vp,
+                                                       _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "poporon_check_planes_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp]),
+    "poporon_encode_planes_strided_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t,
+                                                        C.c_size_t, _vp]),
+    "poporon_decode_planes_strided_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t,
+                                                        C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "poporon_check_planes_strided_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t,
+                                                       C.c_size_t, _vp, _vp]),
     "poporon_rng_create": (_vp, [C.c_int, _vp, C.c_size_t]),
     "poporon_rng_destroy": (None, [_vp]),
     "poporon_rng_next": (C.c_bool, [_vp, _vp, C.c_size_t]),
@@ -178,6 +192,9 @@ REPORT_KERNEL_NAMES = {KERNEL_SNAPSHOT: "snapshot (device copy or rs_snapshot_k)
 KERNEL_CONV_GATHER, KERNEL_CONV_SCATTER = 20, 21
 CONV_KERNEL_NAMES = {KERNEL_CONV_GATHER: "rs_conv_gather_k (stream to rows)",
                      KERNEL_CONV_SCATTER: "rs_conv_scatter_k (rows to stream)"}
+KERNEL_PLANE_GATHER, KERNEL_PLANE_SCATTER = 22, 23
+PLANE_KERNEL_NAMES = {KERNEL_PLANE_GATHER: "rs_plane_gather_k (planes to rows)",
+                      KERNEL_PLANE_SCATTER: "rs_plane_scatter_k (rows to planes)"}
 LDPC_KERNEL_NAMES = {KERNEL_LDPC_ENCODE: "ldpc_encode_k", KERNEL_LDPC_DECODE: "ldpc_decode_k",
                      KERNEL_LDPC_CHECK: "ldpc_check_k"}
 
@@ -240,6 +257,23 @@ def conv_tile(row_bytes: int, branches: int, cell: int) -> int:
     if min(row_bytes, branches, cell) < 0 or max(row_bytes, branches, cell) >= 1 << 64:
         return 0
     return int(load_library().poporon_amd_conv_tile(row_bytes, branches, cell))
+
+
+def plane_tile(row_bytes: int) -> int:
+    """poporon_amd_plane_tile: codewords per workgroup tile of the plane layout kernels; 0 for no row."""
+    if row_bytes < 0 or row_bytes >= 1 << 64:
+        return 0
+    return int(load_library().poporon_amd_plane_tile(row_bytes))
+
+
+def _plane_table(planes):
+    """a host array of device pointers (ints; None or 0: NULL) for the plane calls"""
+    return (C.c_void_p * len(planes))(*[p or None for p in planes])
+
+
+def _lost_list(lost):
+    lost = [] if lost is None else list(lost)
+    return ((C.c_uint8 * len(lost))(*lost) if lost else None), len(lost)
 
 
 def last_error() -> str:
@@ -662,6 +696,55 @@ class Poporon:
     def check_conv_device(self, d_stream, branches, cell, phase, size, count, d_dirty, stream=0):
         self._check(self.lib.poporon_check_conv_device(self.h, d_stream, branches, cell, phase, size, count, d_dirty,
                                                        stream or None), "poporon_check_conv_device")
+
+    # ---- plane layout: stripes across shards (include/poporon_amd.h) ------------------
+    # planes: size + num_roots device pointers (None: NULL), symbol j of codeword c at planes[j] + c;
+    # lost: ascending plane indices (host)
+    def reserve_planes(self, max_codewords):
+        self._check(self.lib.poporon_amd_reserve_planes(self.h, max_codewords), "poporon_amd_reserve_planes")
+
+    def encode_planes_device(self, planes, size, count, stream=0):
+        self._check(self.lib.poporon_encode_planes_device(self.h, _plane_table(planes), size, count, stream or None),
+                    "poporon_encode_planes_device")
+
+    def decode_planes_device(self, planes, size, count, d_ok, lost=None, d_corrected=None, d_dirty=None, stream=0):
+        la, ln = _lost_list(lost)
+        self._check(self.lib.poporon_decode_planes_device(self.h, _plane_table(planes), size, count, la, ln, d_ok,
+                                                          d_corrected, d_dirty, stream or None),
+                    "poporon_decode_planes_device")
+
+    def decode_planes_report_device(self, planes, size, count, d_ok, d_err_num, d_err_pos, d_err_val, report_stride,
+                                    lost=None, d_corrected=None, d_dirty=None, stream=0):
+        la, ln = _lost_list(lost)
+        self._check(self.lib.poporon_decode_planes_report_device(self.h, _plane_table(planes), size, count, la, ln,
+                                                                 d_ok, d_corrected, d_dirty, d_err_num, d_err_pos,
+                                                                 d_err_val, report_stride, stream or None),
+                    "poporon_decode_planes_report_device")
+
+    def check_planes_device(self, planes, size, count, d_dirty, stream=0):
+        self._check(self.lib.poporon_check_planes_device(self.h, _plane_table(planes), size, count, d_dirty,
+                                                         stream or None), "poporon_check_planes_device")
+
+    def encode_planes_strided_device(self, d_data, data_plane_stride, d_parity, parity_plane_stride, size, count,
+                                     stream=0):
+        self._check(self.lib.poporon_encode_planes_strided_device(self.h, d_data, data_plane_stride, d_parity,
+                                                                  parity_plane_stride, size, count, stream or None),
+                    "poporon_encode_planes_strided_device")
+
+    def decode_planes_strided_device(self, d_data, data_plane_stride, d_parity, parity_plane_stride, size, count,
+                                     d_ok, lost=None, d_corrected=None, d_dirty=None, stream=0):
+        la, ln = _lost_list(lost)
+        self._check(self.lib.poporon_decode_planes_strided_device(self.h, d_data, data_plane_stride, d_parity,
+                                                                  parity_plane_stride, size, count, la, ln, d_ok,
+                                                                  d_corrected, d_dirty, stream or None),
+                    "poporon_decode_planes_strided_device")
+
+    def check_planes_strided_device(self, d_data, data_plane_stride, d_parity, parity_plane_stride, size, count,
+                                    d_dirty, stream=0):
+        self._check(self.lib.poporon_check_planes_strided_device(self.h, d_data, data_plane_stride, d_parity,
+                                                                 parity_plane_stride, size, count, d_dirty,
+                                                                 stream or None),
+                    "poporon_check_planes_strided_device")
 
     # ---- in-library kernel timing (HIP events on the launch stream) ---------------
     def timing(self, enable: bool):

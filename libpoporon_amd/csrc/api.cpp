@@ -118,7 +118,7 @@ struct _poporon_config_t {
     uint64_t seed;
 };
 
-#define NKERN 22
+#define NKERN 24
 struct TimedLaunch {
     int kernel;
     hipEvent_t a, b;
@@ -149,6 +149,10 @@ struct GpuCtx {
      * RS_ILV_ROW bytes per codeword allocated; ordered as ilv is */
     uint8_t *rep = nullptr;
     size_t rep_cap = 0;
+    /* the plane calls' erasure lists (rs_planes.hip): plist_cap rows of plane_list_stride bytes, then plist_cap
+     * counts; ordered as ilv is */
+    uint8_t *plist = nullptr;
+    size_t plist_cap = 0;
     /* the wire form's device image (RS_ILV_WIRE_BYTES, rs_device.h); wire_ok: it
      * holds the handle's form as last set (ensure_wire) */
     uint8_t *wire = nullptr;
@@ -1118,7 +1122,7 @@ static void gpu_release(GpuCtx &g)
 {
     const int dev = g.device;
     const bool any = g.ready || g.stream || g.sstream || g.tab || g.gtab || g.rem || g.ltab || g.lws || g.stage ||
-                     g.hstage || g.zc || g.ilv || g.rep || g.wire || g.rslot.stream ||
+                     g.hstage || g.zc || g.ilv || g.rep || g.plist || g.wire || g.rslot.stream ||
                      g.rem_done || g.registered || g.batch_ev ||
                      g.pipe[0].stream || g.pipe[1].stream || g.pipe[2].stream;
     if (!any || dev < 0) {
@@ -1149,6 +1153,7 @@ static void gpu_release(GpuCtx &g)
     (void)hipFree(g.rem);
     (void)hipFree(g.ilv);
     (void)hipFree(g.rep);
+    (void)hipFree(g.plist);
     (void)hipFree(g.wire);
     (void)hipFree(g.ltab);
     (void)hipFree(g.lws);
@@ -3478,6 +3483,280 @@ EXPORT bool poporon_check_conv_device(poporon_t *h, const uint8_t *d_stream, siz
         }
         return rem_release(g, s);
     });
+}
+
+/* ------------------------------------------------------------------------ */
+/* plane layout (storage stripes): layout kernels around the row kernels    */
+/* ------------------------------------------------------------------------ */
+
+/*
+ * A stripe is W = size + num_roots planes, codeword c's symbol j at
+ * planes[j][c] (poporon_amd.h).  plane_run mirrors ilv_run: per chunk of at
+ * most ilv_chunk codewords the planes are gathered into the staging rows of
+ * the interleaved calls (rs_planes.hip), the row launchers run there, routed
+ * by the chunk's count, and the rows are scattered back -- the parity planes
+ * after an encode, every non-NULL plane after a decode, nothing after a check.
+ * The table and the lost set go to the kernels by value.  A rebuild gives every
+ * codeword the same erasure list; the row decoders take per-codeword lists, so
+ * the handle owns a list buffer for one chunk, filled once per call.
+ */
+enum { PLANE_ENCODE, PLANE_DECODE, PLANE_CHECK };
+
+struct PlaneCall {
+    int op;
+    uint8_t *const *planes; /* host array of size + num_roots device pointers */
+    size_t size, count;
+    const uint8_t *lost; /* host array */
+    size_t lost_count;
+    uint8_t *ok, *cor, *dirty;
+    RepOut rep; /* PLANE_DECODE: the report arrays (num NULL: none) */
+};
+
+/* list rows sit on a 16-byte aligned base at a stride that is a multiple of 16: the 32-erasure kernel's fast route */
+static size_t plane_list_stride(const poporon_t *h) { return rs_ws_round16(h->rs->num_roots); }
+
+static bool ensure_plist(poporon_t *h, size_t codewords)
+{
+    GpuCtx &g = h->gpu;
+    if (g.plist_cap >= codewords)
+        return true;
+    if (g.plist) {
+        if (g.rem_pending)
+            HIP_OK(hipEventSynchronize(g.rem_done));
+        g.rem_pending = false;
+        HIP_OK(hipFree(g.plist));
+        g.plist = nullptr;
+        g.plist_cap = 0;
+    }
+    HIP_OK(hipMalloc((void **)&g.plist, codewords * (plane_list_stride(h) + 1)));
+    g.plist_cap = codewords;
+    return true;
+}
+
+/* the checks every plane entry point makes before it touches the GPU */
+static bool plane_args(const poporon_t *h, const char *what, const PlaneCall &c)
+{
+    if (!h)
+        return fail("%s: NULL handle", what);
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("%s serves RS handles", what);
+    if (!check_decode_size(h, c.size))
+        return fail("%s: size %zu outside [1, %u]", what, c.size, (unsigned)kmax(h));
+    const size_t nr = h->rs->num_roots, w = c.size + nr;
+    if (c.lost_count > nr)
+        return fail("%s: lost_count %zu > num_roots (%zu)", what, c.lost_count, nr);
+    if (c.lost_count && !c.lost)
+        return fail("%s: NULL argument (the lost list)", what);
+    for (size_t k = 0; k < c.lost_count; k++) {
+        if (c.lost[k] >= w)
+            return fail("%s: lost plane index %u >= size + num_roots = %zu", what, (unsigned)c.lost[k], w);
+        if (k && c.lost[k] <= c.lost[k - 1])
+            return fail("%s: the lost list is not strictly ascending at entry %zu", what, k);
+    }
+    if (c.count == 0)
+        return true;
+    if (!c.planes || (c.op == PLANE_DECODE && !c.ok) || (c.op == PLANE_CHECK && !c.dirty))
+        return fail("%s: NULL argument", what);
+    size_t k = 0, delivered = 0;
+    for (size_t j = 0; j < w; j++) {
+        const bool is_lost = k < c.lost_count && c.lost[k] == j;
+        k += is_lost;
+        if (c.op == PLANE_ENCODE && j >= c.size)
+            delivered += c.planes[j] != nullptr;
+        else if (!c.planes[j] && !is_lost)
+            return fail("%s: NULL plane %zu", what, j);
+    }
+    if (c.op == PLANE_ENCODE && !delivered)
+        return fail("%s: every parity plane is NULL", what);
+    return true;
+}
+
+/* device pointers in the table; the caller holds the batch scope and the device */
+static bool plane_run(poporon_t *h, const PlaneCall &c, hipStream_t s)
+{
+    GpuCtx &g = h->gpu;
+    const uint32_t nr = h->rs->num_roots, size = (uint32_t)c.size, w = size + nr;
+    const size_t chunk = h->ilv_chunk, n0 = std::min(c.count, chunk), ls = plane_list_stride(h);
+    const bool report = c.op == PLANE_DECODE && c.rep.num;
+    uint32_t lost[8] = {};
+    for (size_t k = 0; k < c.lost_count; k++)
+        lost[c.lost[k] >> 5] |= 1u << (c.lost[k] & 31u);
+    /* the planes a pass touches: the message on the way into an encode, all of them otherwise; on the way out
+     * the parity of an encode, all of a decode */
+    const uint32_t gfirst = 0, glast = c.op == PLANE_ENCODE ? size : w;
+    const uint32_t sfirst = c.op == PLANE_ENCODE ? size : 0, slast = w;
+    uintptr_t low = 0; /* every entry a multiple of 16: the kernels whose plane runs are whole slots */
+    for (uint32_t j = 0; j < w; j++)
+        low |= reinterpret_cast<uintptr_t>(c.planes[j]);
+    if (report && !ensure_rep(h, n0))
+        return false;
+    if (c.lost_count && !ensure_plist(h, n0))
+        return false;
+    if (!ensure_ilv(h, n0) || !rem_acquire(g, s))
+        return false;
+    uint8_t *rows = g.ilv;
+    for (size_t c0 = 0; c0 < c.count; c0 += chunk) {
+        const size_t n = std::min(chunk, c.count - c0);
+        const bool aligned = ((low | c0) & 15u) == 0;
+        {
+            KernelTimer t(g, POPORON_AMD_KERNEL_PLANE_GATHER, s);
+            if (c0 == 0 && c.lost_count) /* one list serves every chunk */
+                HIP_OK(rsk_plane_lists(lost, (uint32_t)c.lost_count, g.plist, (uint32_t)ls, g.plist + g.plist_cap * ls,
+                                       n0, s));
+            HIP_OK(rsk_plane_gather(c.planes, lost, w, gfirst, glast, c0, rows, n, aligned, s));
+            t.done();
+        }
+        if (c.op == PLANE_ENCODE) {
+            if (!launch_encode(h, rows, w, rows + size, w, size, n, s))
+                return false;
+        } else if (c.op == PLANE_DECODE) {
+            const DecodeCall d = {.data = rows, .ds = w, .par = rows + size, .ps = w, .size = size, .count = n,
+                                  .pos8 = c.lost_count ? g.plist : nullptr, .pos_stride = ls,
+                                  .cnt = c.lost_count ? g.plist + g.plist_cap * ls : nullptr, .ok = c.ok + c0,
+                                  .corrected = c.cor ? c.cor + c0 : nullptr, .s = s};
+            if (report && !rep_snapshot(h, d))
+                return false;
+            if (!launch_decode(h, d))
+                return false;
+            if (report && !rep_diff(h, d, c.rep, c0))
+                return false;
+            if (c.dirty && !launch_check(h, rows, w, rows + size, w, size, n, c.dirty + c0, s))
+                return false;
+        } else if (!launch_check(h, rows, w, rows + size, w, size, n, c.dirty + c0, s)) {
+            return false;
+        }
+        if (c.op != PLANE_CHECK)
+            STAGE(g, POPORON_AMD_KERNEL_PLANE_SCATTER, s,
+                  rsk_plane_scatter(rows, c.planes, w, sfirst, slast, c0, n, aligned, s));
+    }
+    return rem_release(g, s);
+}
+
+static bool plane_device(poporon_t *h, const char *what, const PlaneCall &c, void *stream)
+{
+    if (!plane_args(h, what, c) || (c.rep.num && !rep_args(h, what, c.count, c.rep)))
+        return false;
+    if (c.count == 0)
+        return true;
+    if (!batch_enter(h))
+        return false;
+    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
+    DeviceGuard dg(h->gpu.device);
+    return plane_run(h, c, (hipStream_t)stream);
+}
+
+EXPORT size_t poporon_amd_plane_tile(size_t row_bytes)
+{
+    return row_bytes > 255 ? 0 : rsk_plane_tile((uint32_t)row_bytes);
+}
+
+EXPORT bool poporon_amd_reserve_planes(poporon_t *h, size_t max_codewords)
+{
+    if (!h)
+        return fail("NULL handle");
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("poporon_amd_reserve_planes serves RS handles");
+    if (!gpu_init(h))
+        return false;
+    DeviceGuard dg(h->gpu.device);
+    const size_t n = std::min(max_codewords, h->ilv_chunk);
+    return ensure_plist(h, n) && ensure_ilv(h, n) && ensure_rem(h, n);
+}
+
+EXPORT bool poporon_encode_planes_device(poporon_t *h, uint8_t *const *planes, size_t size, size_t count, void *stream)
+{
+    const PlaneCall c = {PLANE_ENCODE, planes, size, count, nullptr, 0, nullptr, nullptr, nullptr, {}};
+    return plane_device(h, "poporon_encode_planes_device", c, stream);
+}
+
+EXPORT bool poporon_decode_planes_device(poporon_t *h, uint8_t *const *planes, size_t size, size_t count,
+                                         const uint8_t *lost, size_t lost_count, uint8_t *d_ok, uint8_t *d_corrected,
+                                         uint8_t *d_dirty, void *stream)
+{
+    const PlaneCall c = {PLANE_DECODE, planes, size, count, lost, lost_count, d_ok, d_corrected, d_dirty, {}};
+    return plane_device(h, "poporon_decode_planes_device", c, stream);
+}
+
+EXPORT bool poporon_decode_planes_report_device(poporon_t *h, uint8_t *const *planes, size_t size, size_t count,
+                                                const uint8_t *lost, size_t lost_count, uint8_t *d_ok,
+                                                uint8_t *d_corrected, uint8_t *d_dirty, uint8_t *d_err_num,
+                                                uint8_t *d_err_pos, uint8_t *d_err_val, size_t report_stride,
+                                                void *stream)
+{
+    const char *what = "poporon_decode_planes_report_device";
+    const PlaneCall c = {PLANE_DECODE, planes, size, count, lost, lost_count, d_ok, d_corrected, d_dirty,
+                         {d_err_num, d_err_pos, d_err_val, report_stride}};
+    /* the plain call is the one without report arrays: here they are required */
+    if (h && h->fec_type == PPLN_FEC_RS && !rep_args(h, what, count, c.rep))
+        return false;
+    return plane_device(h, what, c, stream);
+}
+
+EXPORT bool poporon_check_planes_device(poporon_t *h, const uint8_t *const *planes, size_t size, size_t count,
+                                        uint8_t *d_dirty, void *stream)
+{
+    const PlaneCall c = {PLANE_CHECK, const_cast<uint8_t *const *>(planes), size, count, nullptr, 0, nullptr, nullptr,
+                         d_dirty, {}};
+    return plane_device(h, "poporon_check_planes_device", c, stream);
+}
+
+/* The strided forms: one buffer, message plane j at d_data + j*data_plane_stride, parity plane p at d_parity +
+ * p*parity_plane_stride.  They fill a table on the host and take the table forms' path. */
+static bool plane_table(const poporon_t *h, const char *what, size_t size, size_t count, const uint8_t *d_data,
+                        size_t ds, const uint8_t *d_parity, size_t ps, std::vector<uint8_t *> &tab)
+{
+    if (!h)
+        return fail("%s: NULL handle", what);
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("%s serves RS handles", what);
+    if (!check_decode_size(h, size))
+        return fail("%s: size %zu outside [1, %u]", what, size, (unsigned)kmax(h));
+    if (count && (!d_data || !d_parity))
+        return fail("%s: NULL argument", what);
+    const size_t nr = h->rs->num_roots;
+    tab.resize(size + nr);
+    for (size_t j = 0; j < size; j++)
+        tab[j] = const_cast<uint8_t *>(d_data) + j * ds;
+    for (size_t p = 0; p < nr; p++)
+        tab[size + p] = const_cast<uint8_t *>(d_parity) + p * ps;
+    return true;
+}
+
+EXPORT bool poporon_encode_planes_strided_device(poporon_t *h, const uint8_t *d_data, size_t data_plane_stride,
+                                                 uint8_t *d_parity, size_t parity_plane_stride, size_t size,
+                                                 size_t count, void *stream)
+{
+    const char *what = "poporon_encode_planes_strided_device";
+    std::vector<uint8_t *> tab;
+    if (!plane_table(h, what, size, count, d_data, data_plane_stride, d_parity, parity_plane_stride, tab))
+        return false;
+    const PlaneCall c = {PLANE_ENCODE, tab.data(), size, count, nullptr, 0, nullptr, nullptr, nullptr, {}};
+    return plane_device(h, what, c, stream);
+}
+
+EXPORT bool poporon_decode_planes_strided_device(poporon_t *h, uint8_t *d_data, size_t data_plane_stride,
+                                                 uint8_t *d_parity, size_t parity_plane_stride, size_t size,
+                                                 size_t count, const uint8_t *lost, size_t lost_count, uint8_t *d_ok,
+                                                 uint8_t *d_corrected, uint8_t *d_dirty, void *stream)
+{
+    const char *what = "poporon_decode_planes_strided_device";
+    std::vector<uint8_t *> tab;
+    if (!plane_table(h, what, size, count, d_data, data_plane_stride, d_parity, parity_plane_stride, tab))
+        return false;
+    const PlaneCall c = {PLANE_DECODE, tab.data(), size, count, lost, lost_count, d_ok, d_corrected, d_dirty, {}};
+    return plane_device(h, what, c, stream);
+}
+
+EXPORT bool poporon_check_planes_strided_device(poporon_t *h, const uint8_t *d_data, size_t data_plane_stride,
+                                                const uint8_t *d_parity, size_t parity_plane_stride, size_t size,
+                                                size_t count, uint8_t *d_dirty, void *stream)
+{
+    const char *what = "poporon_check_planes_strided_device";
+    std::vector<uint8_t *> tab;
+    if (!plane_table(h, what, size, count, d_data, data_plane_stride, d_parity, parity_plane_stride, tab))
+        return false;
+    const PlaneCall c = {PLANE_CHECK, tab.data(), size, count, nullptr, 0, nullptr, nullptr, d_dirty, {}};
+    return plane_device(h, what, c, stream);
 }
 
 /* Host form: chunks of rows through one pinned slot of its own and the device

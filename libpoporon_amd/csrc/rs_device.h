@@ -468,6 +468,31 @@ hipError_t rsk_conv_scatter(const uint8_t *data, size_t ds, const uint8_t *parit
                             uint8_t *stream, int path, hipStream_t s);
 
 /*
+ * Plane layout (rs_planes.hip): `planes` is a host array of w = size + nr
+ * device pointers, symbol j of codeword c at planes[j][c]; it travels to the
+ * kernels by value.  `rows` are the wire rows of a chunk (16-byte aligned, w
+ * bytes per codeword), whose codeword 0 is codeword `base` of the planes.
+ *   rsk_plane_gather   planes -> rows.  Planes outside [first, last), planes
+ *                      whose bit is set in the 256-bit mask `lost` (NULL: none)
+ *                      and NULL entries are never read: their columns are 0
+ *   rsk_plane_scatter  rows -> planes [first, last); NULL entries are skipped
+ *   rsk_plane_lists    n erasure lists of `stride` bytes (a multiple of 16, on
+ *                      a 16-byte boundary): the set bits of `lost` ascending,
+ *                      zeros behind them; cnt[c] = lost_count
+ * aligned: every plane pointer that moves, plus base, is a multiple of 16.
+ * Nothing outside [base, base + count) of a plane is read or written.
+ */
+#define RS_PLANE_LDS 32768u     /* LDS bytes of a workgroup's tile of rows at the most */
+#define RS_PLANE_TILE_MAX 512u  /* codewords per workgroup at the most */
+uint32_t rsk_plane_tile(uint32_t w);
+hipError_t rsk_plane_gather(const uint8_t *const *planes, const uint32_t *lost, uint32_t w, uint32_t first,
+                            uint32_t last, size_t base, uint8_t *rows, size_t count, bool aligned, hipStream_t s);
+hipError_t rsk_plane_scatter(const uint8_t *rows, uint8_t *const *planes, uint32_t w, uint32_t first, uint32_t last,
+                             size_t base, size_t count, bool aligned, hipStream_t s);
+hipError_t rsk_plane_lists(const uint32_t *lost, uint32_t lost_count, uint8_t *pos, uint32_t stride, uint8_t *cnt,
+                           size_t n, hipStream_t s);
+
+/*
  * Reports and erasure lists (rs_report.hip): the sparse non-zero bytes of a
  * codeword-shaped region as an ascending list of at most nr entries per
  * codeword, the slots behind the count 0, bytes nr .. stride never written.
