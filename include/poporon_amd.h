@@ -524,6 +524,113 @@ bool poporon_check_planes_strided_device(poporon_t *pprn, const uint8_t *d_data,
                                          const uint8_t *d_parity, size_t parity_plane_stride, size_t size,
                                          size_t count, uint8_t *d_dirty, void *stream);
 
+/* ---- product-code blocks (RS x RS: DVD's RS-PC block, flash and tape) --------
+ * A block is a codeword of a ROW code along every row and of a COLUMN code
+ * along every column.  Its decode is not one call per codeword but a schedule
+ * of row passes and column passes that hand each other their failures as
+ * erasures.  These calls run that schedule on the device without returning to
+ * the host between passes.
+ *
+ * Object.  poporon_amd_product_create takes two RS configs that
+ * poporon_amd_supported serves, with the SAME symbol_size and the SAME field
+ * polynomial (anything else: NULL with a message); fcr, prim and num_roots may
+ * differ.  With one field both encodes are linear over it, so the checks on
+ * checks are the same whichever axis is encoded first and the encoded block is
+ * a codeword on every row and every column (tests/test_product_cpu.py shows it
+ * on the reference).  The object owns one handle per axis
+ * (poporon_amd_product_handle: 0 = row code, 1 = column code; for
+ * poporon_amd_timing and poporon_amd_set_device on axis 0 BEFORE the first GPU
+ * call; the column handle follows the row handle's device).  Create needs no
+ * GPU.
+ *
+ * Layout.  The row code takes messages of row_size = k1 symbols, n1 = k1 + r1;
+ * the column code col_size = k2, n2 = k2 + r2 (poporon_amd_product_shape gives
+ * n1 and n2, no GPU).  Block b is n2 rows of n1 bytes, byte (i, j) at d_blocks +
+ * b*block_stride + i*row_pitch + j.  Rows 0 .. k2-1 x columns 0 .. k1-1 are the
+ * message, rows k2 .. n2-1 column parity, columns k1 .. n1-1 row parity.
+ * row_pitch >= n1 and block_stride >= (n2-1)*row_pitch + n1; any base alignment;
+ * all offsets size_t; bytes of a pitch or a stride outside the n2 x n1 rectangle
+ * are never written.  Row codeword (b, i) has per-codeword index b*n2 + i,
+ * column codeword (b, j) index b*n1 + j and its symbol i is byte (i, j): a
+ * column's erasure positions are row indices, parity rows k2 .. n2-1.
+ *
+ * Calls (asynchronous on `stream`; count in blocks; count 0 succeeds and
+ * launches nothing):
+ *  - poporon_encode_product_device reads the message rectangle only, writes the
+ *    column parity of columns 0 .. k1-1 (the column code's encode on the
+ *    columns), then the row parity of all n2 rows.
+ *  - poporon_check_product_device: d_row_dirty[b*n2 + i] and d_col_dirty[b*n1 +
+ *    j] are poporon_check_batch_device's flag on that codeword, d_block_ok[b] =
+ *    1 iff none of the block's flags is set.  Any output may be NULL, not all.
+ *  - poporon_decode_product_device: pass p = 0 .. passes-1 (1 <= passes <= 16)
+ *    runs on axis A = (first_axis + p) mod 2:
+ *     1. Lists.  With couple != 0 and p > 0 let E_b be the ascending indices of
+ *        the OTHER axis's codewords of block b that are dirty after pass p-1,
+ *        r_A the num_roots of A's code.  If floor(r_A/2) < |E_b| <= r_A every
+ *        A-codeword of block b gets the erasure list E_b, zeros behind it up to
+ *        r_A, and the count |E_b| (the fill
+ *        poporon_amd_erasures_from_mask_device writes); otherwise a list of
+ *        zeros with the count 0.  With p = 0 or couple == 0 the pass is the
+ *        errors-only call (d_positions NULL).
+ *        NOTE: a count-0 list is NOT the errors-only call.  It is the erasure
+ *        mode of the reference with an empty list, and in that mode the
+ *        reference XORs magnitude i into list slot i, read past the count
+ *        (quirk Q2): a codeword with 1 .. t errors comes back ok with every
+ *        magnitude XORed into symbol 0, and step 3 flags it dirty.  Clean and
+ *        undecodable codewords are unaffected.  So a coupled pass repairs
+ *        erasures where the other axis flagged floor(r_A/2)+1 .. r_A codewords
+ *        and repairs NO plain errors anywhere; a schedule that needs the
+ *        errors-only decode on a later pass asks for it with couple == 0
+ *        (tests/test_product_cpu.py pins this on the reference).
+ *     2. Decode: poporon_decode_batch_device on the A-codewords with those
+ *        lists, bit for bit, Q1/Q2 and failed codewords as that call leaves
+ *        them.
+ *     3. Flags: poporon_check_batch_device on the A-codewords as written back.
+ *        "Failed" means dirty after the pass, not !ok: that catches a Q2 result.
+ *    After the last pass the other axis is checked once; the three outputs mean
+ *    what they mean in the check call, on the block as returned.
+ *  - poporon_encode_product / poporon_decode_product: the same on host memory,
+ *    whole blocks through a pinned slot, returning when the results are there.
+ *
+ * How: chunks of whole blocks, at most POPORON_AMD_ILV_CHUNK codewords of
+ * either axis, run one after another; a chunk's whole schedule is enqueued
+ * before the next chunk's.  A pass gathers the axis's codewords into that
+ * handle's staging rows (rs_product.hip), runs the row kernels there, routed by
+ * the chunk's codeword count, and scatters them back: the whole rectangle after
+ * a decode, that pass's parity after an encode, nothing after a check.  When
+ * block_stride == n2*row_pitch the rows are wire rows already and the row code
+ * runs in place on the caller's buffer (no staging, no timing id).  The lists
+ * live in the axis handle's list buffer (the plane calls'), on a 16-byte
+ * aligned base at a stride of r_A rounded up to 16.  A NULL flag output is
+ * replaced by a workspace the object owns.  poporon_amd_product_reserve sizes
+ * all of it for min(max_blocks, a chunk) blocks, after which product calls
+ * allocate nothing.  poporon_amd_product_tile gives the layout kernels' tile for
+ * blocks of `codewords` codewords of codeword_bytes each on an axis (axis 1:
+ * n2 and n1; axis 0: n1 and n2): *blocks whole blocks per workgroup, and
+ * *per_tile codewords of a block per workgroup (= codewords unless a block is
+ * split; then *blocks is 1).  No GPU.  There are no report forms. */
+typedef struct _poporon_product_t poporon_product_t;
+poporon_product_t *poporon_amd_product_create(const poporon_config_t *row_config, const poporon_config_t *col_config);
+void poporon_amd_product_destroy(poporon_product_t *prod);
+poporon_t *poporon_amd_product_handle(poporon_product_t *prod, int axis);
+bool poporon_amd_product_shape(const poporon_product_t *prod, size_t row_size, size_t col_size, size_t *n1, size_t *n2);
+bool poporon_amd_product_tile(size_t codeword_bytes, size_t codewords, size_t *blocks, size_t *per_tile);
+bool poporon_amd_product_reserve(poporon_product_t *prod, size_t row_size, size_t col_size, size_t max_blocks);
+bool poporon_encode_product_device(poporon_product_t *prod, uint8_t *d_blocks, size_t row_pitch, size_t block_stride,
+                                   size_t row_size, size_t col_size, size_t count, void *stream);
+bool poporon_decode_product_device(poporon_product_t *prod, uint8_t *d_blocks, size_t row_pitch, size_t block_stride,
+                                   size_t row_size, size_t col_size, size_t count, int first_axis, size_t passes,
+                                   int couple, uint8_t *d_row_dirty, uint8_t *d_col_dirty, uint8_t *d_block_ok,
+                                   void *stream);
+bool poporon_check_product_device(poporon_product_t *prod, const uint8_t *d_blocks, size_t row_pitch,
+                                  size_t block_stride, size_t row_size, size_t col_size, size_t count,
+                                  uint8_t *d_row_dirty, uint8_t *d_col_dirty, uint8_t *d_block_ok, void *stream);
+bool poporon_encode_product(poporon_product_t *prod, uint8_t *blocks, size_t row_pitch, size_t block_stride,
+                            size_t row_size, size_t col_size, size_t count);
+bool poporon_decode_product(poporon_product_t *prod, uint8_t *blocks, size_t row_pitch, size_t block_stride,
+                            size_t row_size, size_t col_size, size_t count, int first_axis, size_t passes, int couple,
+                            uint8_t *row_dirty, uint8_t *col_dirty, uint8_t *block_ok);
+
 /* ---- LDPC batches -----------------------------------------------------------
  * Row c has info_bytes (poporon_get_info_size) of data at d_data +
  * c*data_stride and parity_bytes (poporon_get_parity_size) of parity at
@@ -627,6 +734,13 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
  * 23 = rows back to planes (rs_plane_scatter_k), one each per chunk: 22 alone
  * for a check, 23 only the parity planes for an encode; the codec kernels
  * between them keep their ids, d_dirty is one more launch of 3.
+ * The product calls, read on the axis's handle (poporon_amd_product_handle):
+ * 24 = block to staging rows (rs_prod_gather_k), 25 = rows back to the block
+ * (rs_prod_scatter_k), one each per staged pass and chunk (a check: 24 alone),
+ * neither on the in-place row route; 26 = rs_prod_lists_k, one per coupled
+ * pass and chunk on the pass's handle, and rs_prod_ok_k, one per chunk on the
+ * row handle when d_block_ok is given.  The codec kernels keep their ids; a
+ * pass's flags are one more launch of 3.
  *
  * Error- and erasure-mode batches of at least 16384 codewords take the split
  * decode; POPORON_AMD_DECODE_PATH=split / single / wave in the environment
@@ -656,6 +770,7 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
 #define POPORON_AMD_KERNEL_CONV_SCATTER 21
 /* the plane calls' ids are enumerators: tests/test_conv_cpu.py pins the macro ids above to 22 of them */
 enum { POPORON_AMD_KERNEL_PLANE_GATHER = 22, POPORON_AMD_KERNEL_PLANE_SCATTER = 23 };
+enum { POPORON_AMD_KERNEL_PROD_GATHER = 24, POPORON_AMD_KERNEL_PROD_SCATTER = 25, POPORON_AMD_KERNEL_PROD_LISTS = 26 };
 bool poporon_amd_timing(poporon_t *pprn, int enable);
 bool poporon_amd_timing_read(poporon_t *pprn, int kernel, double *total_ms, uint64_t *launches);
 

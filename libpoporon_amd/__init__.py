@@ -141,6 +141,22 @@ _SIGS = {
                                                         C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     "poporon_check_planes_strided_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t,
                                                        C.c_size_t, _vp, _vp]),
+    "poporon_amd_product_create": (_vp, [_vp, _vp]),
+    "poporon_amd_product_destroy": (None, [_vp]),
+    "poporon_amd_product_handle": (_vp, [_vp, C.c_int]),
+    "poporon_amd_product_shape": (C.c_bool, [_vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t),
+                                             C.POINTER(C.c_size_t)]),
+    "poporon_amd_product_tile": (C.c_bool, [C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "poporon_amd_product_reserve": (C.c_bool, [_vp, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "poporon_encode_product_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                 _vp]),
+    "poporon_decode_product_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                 C.c_int, C.c_size_t, C.c_int, _vp, _vp, _vp, _vp]),
+    "poporon_check_product_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                _vp, _vp, _vp, _vp]),
+    "poporon_encode_product": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "poporon_decode_product": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                          C.c_int, C.c_size_t, C.c_int, _vp, _vp, _vp]),
     "poporon_rng_create": (_vp, [C.c_int, _vp, C.c_size_t]),
     "poporon_rng_destroy": (None, [_vp]),
     "poporon_rng_next": (C.c_bool, [_vp, _vp, C.c_size_t]),
@@ -195,6 +211,10 @@ CONV_KERNEL_NAMES = {KERNEL_CONV_GATHER: "rs_conv_gather_k (stream to rows)",
 KERNEL_PLANE_GATHER, KERNEL_PLANE_SCATTER = 22, 23
 PLANE_KERNEL_NAMES = {KERNEL_PLANE_GATHER: "rs_plane_gather_k (planes to rows)",
                       KERNEL_PLANE_SCATTER: "rs_plane_scatter_k (rows to planes)"}
+KERNEL_PROD_GATHER, KERNEL_PROD_SCATTER, KERNEL_PROD_LISTS = 24, 25, 26
+PROD_KERNEL_NAMES = {KERNEL_PROD_GATHER: "rs_prod_gather_k (block to rows)",
+                     KERNEL_PROD_SCATTER: "rs_prod_scatter_k (rows to block)",
+                     KERNEL_PROD_LISTS: "rs_prod_lists_k / rs_prod_ok_k"}
 LDPC_KERNEL_NAMES = {KERNEL_LDPC_ENCODE: "ldpc_encode_k", KERNEL_LDPC_DECODE: "ldpc_decode_k",
                      KERNEL_LDPC_CHECK: "ldpc_check_k"}
 
@@ -264,6 +284,17 @@ def plane_tile(row_bytes: int) -> int:
     if row_bytes < 0 or row_bytes >= 1 << 64:
         return 0
     return int(load_library().poporon_amd_plane_tile(row_bytes))
+
+
+def product_tile(codeword_bytes: int, codewords: int):
+    """poporon_amd_product_tile: (whole blocks per workgroup tile, codewords of a block per tile) of the product
+    layout kernels for blocks of `codewords` codewords of codeword_bytes; None for no such block."""
+    if min(codeword_bytes, codewords) < 0 or max(codeword_bytes, codewords) >= 1 << 64:
+        return None
+    g, u = C.c_size_t(0), C.c_size_t(0)
+    if not load_library().poporon_amd_product_tile(codeword_bytes, codewords, C.byref(g), C.byref(u)):
+        return None
+    return int(g.value), int(u.value)
 
 
 def _plane_table(planes):
@@ -1050,6 +1081,111 @@ class Multi:
     def close(self):
         if getattr(self, "h", None):
             self.lib.poporon_amd_multi_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+class _Borrowed(Poporon):
+    """a handle another object owns: never destroyed from here"""
+
+    def close(self):
+        self.h = None
+
+    __del__ = close
+
+
+class Product:
+    """poporon_product_t (include/poporon_amd.h): RS x RS product-code blocks, a row code and a column code
+    over one field.  ``row`` / ``col``: (symbol_size, generator_polynomial, first_consecutive_root,
+    primitive_element, num_roots).  Block b is n2 rows of n1 bytes, byte (i, j) at d_blocks + b*block_stride +
+    i*row_pitch + j; count is in blocks."""
+
+    def __init__(self, row, col, device: int | None = None):
+        self.lib = load_library()
+        cfgs = [self.lib.poporon_rs_config_create(*p, None, None) for p in (row, col)]
+        try:
+            if not all(cfgs):
+                raise PoporonError("poporon_rs_config_create returned NULL")
+            self.h = self.lib.poporon_amd_product_create(*cfgs)
+        finally:
+            for c in cfgs:
+                if c:
+                    self.lib.poporon_config_destroy(c)
+        if not self.h:
+            raise PoporonError(f"poporon_amd_product_create failed: {last_error()}")
+        self.row_roots, self.col_roots = row[4], col[4]
+        if device is not None:
+            self._check(self.lib.poporon_amd_set_device(self.handle(0).h, device), "poporon_amd_set_device")
+
+    def _check(self, ok, what):
+        if not ok:
+            raise PoporonError(f"{what} failed: {last_error()}")
+
+    def handle(self, axis):
+        """the axis's own handle (0: row code, 1: column code) as a Poporon that does not own it: timing()"""
+        h = self.lib.poporon_amd_product_handle(self.h, axis)
+        if not h:
+            raise PoporonError("poporon_amd_product_handle: axis is neither 0 nor 1")
+        p = _Borrowed.__new__(_Borrowed)
+        p.lib, p.h, p.erasure, p._syn = self.lib, h, None, None
+        p.num_roots = (self.row_roots, self.col_roots)[axis]
+        p._owner = self
+        return p
+
+    def shape(self, row_size, col_size):
+        n1, n2 = C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.poporon_amd_product_shape(self.h, row_size, col_size, C.byref(n1), C.byref(n2)),
+                    "poporon_amd_product_shape")
+        return int(n1.value), int(n2.value)
+
+    def reserve(self, row_size, col_size, max_blocks):
+        self._check(self.lib.poporon_amd_product_reserve(self.h, row_size, col_size, max_blocks),
+                    "poporon_amd_product_reserve")
+
+    def encode_device(self, d_blocks, row_pitch, block_stride, row_size, col_size, count, stream=0):
+        self._check(self.lib.poporon_encode_product_device(self.h, d_blocks, row_pitch, block_stride, row_size,
+                                                           col_size, count, stream or None),
+                    "poporon_encode_product_device")
+
+    def decode_device(self, d_blocks, row_pitch, block_stride, row_size, col_size, count, first_axis=0, passes=2,
+                      couple=1, d_row_dirty=None, d_col_dirty=None, d_block_ok=None, stream=0):
+        self._check(self.lib.poporon_decode_product_device(self.h, d_blocks, row_pitch, block_stride, row_size,
+                                                           col_size, count, first_axis, passes, couple, d_row_dirty,
+                                                           d_col_dirty, d_block_ok, stream or None),
+                    "poporon_decode_product_device")
+
+    def check_device(self, d_blocks, row_pitch, block_stride, row_size, col_size, count, d_row_dirty=None,
+                     d_col_dirty=None, d_block_ok=None, stream=0):
+        self._check(self.lib.poporon_check_product_device(self.h, d_blocks, row_pitch, block_stride, row_size,
+                                                          col_size, count, d_row_dirty, d_col_dirty, d_block_ok,
+                                                          stream or None), "poporon_check_product_device")
+
+    def encode(self, messages):
+        """host form on packed blocks: u8[count, k2, k1] messages -> u8[count, n2, n1] encoded blocks"""
+        m = np.ascontiguousarray(messages, dtype=np.uint8)
+        count, k2, k1 = m.shape
+        n1, n2 = self.shape(k1, k2)
+        out = np.zeros((count, n2, n1), np.uint8)
+        out[:, :k2, :k1] = m
+        self._check(self.lib.poporon_encode_product(self.h, _buf(out), n1, n1 * n2, k1, k2, count),
+                    "poporon_encode_product")
+        return out
+
+    def decode(self, blocks, row_size, col_size, first_axis=0, passes=2, couple=1):
+        """host form on packed blocks u8[count, n2, n1]: (blocks', row_dirty u8[count, n2], col_dirty u8[count, n1],
+        block_ok u8[count])"""
+        b = np.array(blocks, dtype=np.uint8, copy=True, order="C")
+        count, n2, n1 = b.shape
+        rd, cd, ok = np.zeros((count, n2), np.uint8), np.zeros((count, n1), np.uint8), np.zeros(count, np.uint8)
+        self._check(self.lib.poporon_decode_product(self.h, _buf(b), n1, n1 * n2, row_size, col_size, count,
+                                                    first_axis, passes, couple, _buf(rd), _buf(cd), _buf(ok)),
+                    "poporon_decode_product")
+        return b, rd, cd, ok
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.poporon_amd_product_destroy(self.h)
             self.h = None
 
     __del__ = close

@@ -118,7 +118,7 @@ struct _poporon_config_t {
     uint64_t seed;
 };
 
-#define NKERN 24
+#define NKERN 27
 struct TimedLaunch {
     int kernel;
     hipEvent_t a, b;
@@ -3867,6 +3867,450 @@ EXPORT bool poporon_amd_erasures_from_mask_device(poporon_t *h, const uint8_t *d
         t.done();
     }
     return true;
+}
+
+/* ------------------------------------------------------------------------ */
+/* product-code blocks: a schedule of row passes and column passes          */
+/* ------------------------------------------------------------------------ */
+
+/*
+ * A block is a codeword of the row code along every row and of the column code
+ * along every column (poporon_amd.h).  poporon_product_t owns one handle per
+ * axis on one device.  prod_run mirrors plane_run: per chunk of whole blocks,
+ * at most ilv_chunk codewords of either axis, the whole schedule is enqueued
+ * -- per pass the erasure lists from the other axis's flags (rs_prod_lists_k),
+ * the axis's codewords gathered into its handle's staging rows
+ * (rs_product.hip), the row launchers there, routed by the chunk's count, the
+ * check kernel for the pass's flags, and the rows scattered back.  Rows of a
+ * block stack (bstride == n2 * pitch) are wire rows already: the row code runs
+ * on the caller's buffer.  The flags live in the caller's arrays or, where it
+ * passed NULL, in the object's workspace, which also holds the d_ok the row
+ * decoders write.  Nothing waits for the host.
+ */
+struct _poporon_product_t {
+    poporon_t *h[2]; /* 0: the row code, 1: the column code */
+    uint8_t *ws;     /* device: [row flags n2 nb | column flags n1 nb | ok max(n1, n2) nb] of one chunk */
+    size_t ws_bytes;
+};
+
+enum { PROD_ENCODE, PROD_DECODE, PROD_CHECK };
+
+struct ProdCall {
+    int op;
+    uint8_t *blocks;
+    size_t pitch, bstride, k1, k2, count;
+    int first_axis;
+    size_t passes;
+    int couple;
+    uint8_t *row_dirty, *col_dirty, *block_ok;
+};
+
+EXPORT void poporon_amd_product_destroy(poporon_product_t *p)
+{
+    if (!p)
+        return;
+    if (p->ws && p->h[0] && p->h[0]->gpu.ready) {
+        DeviceGuard dg(p->h[0]->gpu.device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(p->ws);
+    }
+    poporon_destroy(p->h[0]);
+    poporon_destroy(p->h[1]);
+    delete p;
+}
+
+EXPORT poporon_product_t *poporon_amd_product_create(const poporon_config_t *row_config,
+                                                     const poporon_config_t *col_config)
+{
+    if (!row_config || !col_config) {
+        fail("poporon_amd_product_create: NULL config");
+        return nullptr;
+    }
+    if (row_config->fec_type != PPLN_FEC_RS || col_config->fec_type != PPLN_FEC_RS) {
+        fail("poporon_amd_product_create serves RS configs");
+        return nullptr;
+    }
+    if (row_config->symbol_size != col_config->symbol_size ||
+        row_config->generator_polynomial != col_config->generator_polynomial) {
+        fail("poporon_amd_product_create: the row code and the column code need one field (symbol_size %u / %u, "
+             "polynomial 0x%X / 0x%X)",
+             (unsigned)row_config->symbol_size, (unsigned)col_config->symbol_size,
+             (unsigned)row_config->generator_polynomial, (unsigned)col_config->generator_polynomial);
+        return nullptr;
+    }
+    poporon_product_t *p = new (std::nothrow) _poporon_product_t();
+    if (!p)
+        return nullptr;
+    p->ws = nullptr;
+    p->ws_bytes = 0;
+    p->h[0] = poporon_create(row_config);
+    p->h[1] = poporon_create(col_config);
+    for (int a = 0; a < 2; a++) {
+        if (!p->h[a] || !p->h[a]->supported) {
+            poporon_amd_product_destroy(p);
+            fail("poporon_amd_product_create: the %s config is not served by the GPU kernels", a ? "column" : "row");
+            return nullptr;
+        }
+    }
+    return p;
+}
+
+EXPORT poporon_t *poporon_amd_product_handle(poporon_product_t *p, int axis)
+{
+    return (p && (axis == 0 || axis == 1)) ? p->h[axis] : nullptr;
+}
+
+EXPORT bool poporon_amd_product_shape(const poporon_product_t *p, size_t row_size, size_t col_size, size_t *n1,
+                                      size_t *n2)
+{
+    if (!p)
+        return fail("poporon_amd_product_shape: NULL handle");
+    if (!check_decode_size(p->h[0], row_size))
+        return fail("poporon_amd_product_shape: row_size %zu outside [1, %u]", row_size, (unsigned)kmax(p->h[0]));
+    if (!check_decode_size(p->h[1], col_size))
+        return fail("poporon_amd_product_shape: col_size %zu outside [1, %u]", col_size, (unsigned)kmax(p->h[1]));
+    if (n1)
+        *n1 = row_size + p->h[0]->rs->num_roots;
+    if (n2)
+        *n2 = col_size + p->h[1]->rs->num_roots;
+    return true;
+}
+
+EXPORT bool poporon_amd_product_tile(size_t codeword_bytes, size_t codewords, size_t *blocks, size_t *per_tile)
+{
+    uint32_t g = 0, u = 0, tpb = 0;
+    if (codeword_bytes > 255 || codewords > 255 ||
+        !rsk_prod_tile((uint32_t)codeword_bytes, (uint32_t)codewords, &g, &u, &tpb))
+        return fail("poporon_amd_product_tile: no block of %zu codewords of %zu bytes", codewords, codeword_bytes);
+    if (blocks)
+        *blocks = g;
+    if (per_tile)
+        *per_tile = u;
+    return true;
+}
+
+/* the checks every product entry point makes before it touches the GPU */
+static bool prod_args(const poporon_product_t *p, const char *what, const ProdCall &c)
+{
+    if (!p)
+        return fail("%s: NULL handle", what);
+    if (!check_decode_size(p->h[0], c.k1))
+        return fail("%s: row_size %zu outside [1, %u]", what, c.k1, (unsigned)kmax(p->h[0]));
+    if (!check_decode_size(p->h[1], c.k2))
+        return fail("%s: col_size %zu outside [1, %u]", what, c.k2, (unsigned)kmax(p->h[1]));
+    const size_t n1 = c.k1 + p->h[0]->rs->num_roots, n2 = c.k2 + p->h[1]->rs->num_roots;
+    if (c.pitch < n1)
+        return fail("%s: row_pitch %zu < row_size + num_roots = %zu", what, c.pitch, n1);
+    if (c.pitch > ((size_t)-1 - n1) / n2 || c.bstride < (n2 - 1) * c.pitch + n1)
+        return fail("%s: block_stride %zu < (n2 - 1) * row_pitch + n1 = %zu", what, c.bstride,
+                    (n2 - 1) * c.pitch + n1);
+    if (c.op == PROD_DECODE) {
+        if (c.first_axis != 0 && c.first_axis != 1)
+            return fail("%s: first_axis %d is neither 0 nor 1", what, c.first_axis);
+        if (c.passes < 1 || c.passes > 16)
+            return fail("%s: passes %zu outside [1, 16]", what, c.passes);
+    }
+    if (c.op != PROD_ENCODE && !c.row_dirty && !c.col_dirty && !c.block_ok)
+        return fail("%s: NULL argument (d_row_dirty, d_col_dirty and d_block_ok)", what);
+    if (c.count == 0)
+        return true;
+    if (!c.blocks)
+        return fail("%s: NULL argument (the blocks)", what);
+    if (c.count > ((size_t)-1) / c.bstride)
+        return fail("%s: count * block_stride passes size_t", what);
+    return true;
+}
+
+/* blocks per chunk: at most ilv_chunk codewords on either axis, at least one block */
+static size_t prod_chunk(const poporon_product_t *p, size_t n1, size_t n2)
+{
+    return std::max<size_t>(1, p->h[0]->ilv_chunk / std::max(n1, n2));
+}
+
+/* both handles' device contexts on one device, no live server beside the batch */
+static bool prod_enter(poporon_product_t *p)
+{
+    if (!batch_enter(p->h[0]))
+        return false;
+    if (!p->h[1]->gpu.ready && !poporon_amd_set_device(p->h[1], p->h[0]->gpu.device)) {
+        batch_exit(p->h[0]->gpu, nullptr, true);
+        return false;
+    }
+    if (!batch_enter(p->h[1])) {
+        batch_exit(p->h[0]->gpu, nullptr, true);
+        return false;
+    }
+    return true;
+}
+
+/* the object's workspace for chunks of nb blocks; its last reader ran under both handles' rem ordering */
+static bool prod_ensure_ws(poporon_product_t *p, size_t n1, size_t n2, size_t nb)
+{
+    const size_t need = nb * (n1 + n2 + std::max(n1, n2));
+    if (p->ws_bytes >= need)
+        return true;
+    if (p->ws) {
+        for (int a = 0; a < 2; a++) {
+            GpuCtx &g = p->h[a]->gpu;
+            if (g.rem_pending)
+                HIP_OK(hipEventSynchronize(g.rem_done));
+            g.rem_pending = false;
+        }
+        HIP_OK(hipFree(p->ws));
+        p->ws = nullptr;
+        p->ws_bytes = 0;
+    }
+    HIP_OK(hipMalloc((void **)&p->ws, need));
+    p->ws_bytes = need;
+    return true;
+}
+
+static bool prod_reserve(poporon_product_t *p, size_t n1, size_t n2, size_t nb)
+{
+    return prod_ensure_ws(p, n1, n2, nb) && ensure_ilv(p->h[0], nb * n2) && ensure_ilv(p->h[1], nb * n1) &&
+           ensure_rem(p->h[0], nb * n2) && ensure_rem(p->h[1], nb * n1) && ensure_plist(p->h[0], nb * n2) &&
+           ensure_plist(p->h[1], nb * n1);
+}
+
+/* device pointers; the caller holds both batch scopes and the device */
+static bool prod_run(poporon_product_t *p, const ProdCall &c, hipStream_t s)
+{
+    poporon_t *h0 = p->h[0], *h1 = p->h[1];
+    const uint32_t k[2] = {(uint32_t)c.k1, (uint32_t)c.k2};
+    const uint32_t r[2] = {h0->rs->num_roots, h1->rs->num_roots};
+    const uint32_t n[2] = {k[0] + r[0], k[1] + r[1]}; /* n[a]: bytes of an axis-a codeword */
+    const uint32_t cwn[2] = {n[1], n[0]};             /* codewords of axis a in a block */
+    const size_t chunk = prod_chunk(p, n[0], n[1]), nb0 = std::min(c.count, chunk);
+    const bool inplace = c.bstride == (size_t)n[1] * c.pitch; /* the blocks' rows are wire rows at stride pitch */
+    if (!prod_ensure_ws(p, n[0], n[1], nb0))
+        return false;
+    if (!ensure_ilv(h1, nb0 * n[0]) || ((!inplace) && !ensure_ilv(h0, nb0 * n[1])))
+        return false;
+    if (c.op == PROD_DECODE && c.couple) /* passes 1, 2, ... take lists: the second axis, then the first again */
+        for (size_t pass = 1; pass < std::min<size_t>(c.passes, 3); pass++) {
+            const int a = (c.first_axis + (int)pass) & 1;
+            if (!ensure_plist(p->h[a], nb0 * cwn[a]))
+                return false;
+        }
+    if (!rem_acquire(h0->gpu, s) || !rem_acquire(h1->gpu, s))
+        return false;
+    for (size_t b0 = 0; b0 < c.count; b0 += chunk) {
+        const size_t nb = std::min(chunk, c.count - b0);
+        uint8_t *blk = c.blocks + b0 * c.bstride;
+        uint8_t *flag[2] = {c.row_dirty ? c.row_dirty + b0 * n[1] : p->ws,
+                            c.col_dirty ? c.col_dirty + b0 * n[0] : p->ws + nb0 * n[1]};
+        uint8_t *okbuf = p->ws + nb0 * (n[0] + n[1]);
+        /* axis a's codewords of the chunk as rows: where they are, gathered first unless they are the block rows */
+        auto stage = [&](int a, uint32_t cw, uint32_t m1, uint8_t *&data, size_t &ds) -> bool {
+            poporon_t *h = p->h[a];
+            if (a == 0 && inplace) {
+                data = blk;
+                ds = c.pitch;
+                return true;
+            }
+            data = h->gpu.ilv;
+            ds = n[a];
+            STAGE(h->gpu, POPORON_AMD_KERNEL_PROD_GATHER, s,
+                  rsk_prod_gather(blk, c.pitch, c.bstride, nb, (uint32_t)a, n[a], cw, 0u, m1, data, s));
+            return true;
+        };
+        auto unstage = [&](int a, uint32_t cw, uint32_t m0) -> bool {
+            poporon_t *h = p->h[a];
+            if (a == 0 && inplace)
+                return true;
+            STAGE(h->gpu, POPORON_AMD_KERNEL_PROD_SCATTER, s,
+                  rsk_prod_scatter(h->gpu.ilv, blk, c.pitch, c.bstride, nb, (uint32_t)a, n[a], cw, m0, n[a], s));
+            return true;
+        };
+        auto check = [&](int a) -> bool {
+            uint8_t *data;
+            size_t ds;
+            return stage(a, cwn[a], n[a], data, ds) &&
+                   launch_check(p->h[a], data, ds, data + k[a], ds, k[a], nb * cwn[a], flag[a], s);
+        };
+        if (c.op == PROD_ENCODE) {
+            /* column parity of the message columns, then row parity of every row: the checks on checks come out
+             * the same either way round (one field) */
+            for (int a = 1; a >= 0; a--) {
+                const uint32_t cw = a ? k[0] : n[1];
+                uint8_t *data;
+                size_t ds;
+                if (!stage(a, cw, k[a], data, ds) ||
+                    !launch_encode(p->h[a], data, ds, data + k[a], ds, k[a], nb * cw, s) || !unstage(a, cw, k[a]))
+                    return false;
+            }
+            continue;
+        }
+        if (c.op == PROD_CHECK) {
+            if (!check(0) || !check(1))
+                return false;
+        } else {
+            int a = c.first_axis;
+            for (size_t pass = 0; pass < c.passes; pass++, a ^= 1) {
+                poporon_t *h = p->h[a];
+                GpuCtx &g = h->gpu;
+                const size_t ls = plane_list_stride(h), ncw = nb * cwn[a];
+                const bool lists = c.couple && pass > 0;
+                if (lists)
+                    STAGE(g, POPORON_AMD_KERNEL_PROD_LISTS, s,
+                          rsk_prod_lists(flag[a ^ 1], n[a], r[a], cwn[a], g.plist, (uint32_t)ls,
+                                         g.plist + g.plist_cap * ls, nb, s));
+                uint8_t *data;
+                size_t ds;
+                if (!stage(a, cwn[a], n[a], data, ds))
+                    return false;
+                const DecodeCall d = {.data = data, .ds = ds, .par = data + k[a], .ps = ds, .size = k[a], .count = ncw,
+                                      .pos8 = lists ? g.plist : nullptr, .pos_stride = ls,
+                                      .cnt = lists ? g.plist + g.plist_cap * ls : nullptr, .ok = okbuf,
+                                      .corrected = nullptr, .s = s};
+                if (!launch_decode(h, d) || !launch_check(h, data, ds, data + k[a], ds, k[a], ncw, flag[a], s) ||
+                    !unstage(a, cwn[a], 0u))
+                    return false;
+            }
+            if (!check(a)) /* the axis the last pass did not run on, on the block as returned */
+                return false;
+        }
+        if (c.block_ok)
+            STAGE(h0->gpu, POPORON_AMD_KERNEL_PROD_LISTS, s,
+                  rsk_prod_ok(flag[0], n[1], flag[1], n[0], c.block_ok + b0, nb, s));
+    }
+    return rem_release(h0->gpu, s) && rem_release(h1->gpu, s);
+}
+
+static bool prod_device(poporon_product_t *p, const char *what, const ProdCall &c, void *stream)
+{
+    if (!prod_args(p, what, c))
+        return false;
+    if (c.count == 0)
+        return true;
+    if (!prod_enter(p))
+        return false;
+    BatchScope bs0{p->h[0]->gpu, (hipStream_t)stream, false}, bs1{p->h[1]->gpu, (hipStream_t)stream, false};
+    DeviceGuard dg(p->h[0]->gpu.device);
+    return prod_run(p, c, (hipStream_t)stream);
+}
+
+EXPORT bool poporon_amd_product_reserve(poporon_product_t *p, size_t row_size, size_t col_size, size_t max_blocks)
+{
+    size_t n1 = 0, n2 = 0;
+    if (!p)
+        return fail("poporon_amd_product_reserve: NULL handle");
+    if (!poporon_amd_product_shape(p, row_size, col_size, &n1, &n2))
+        return false;
+    if (!gpu_init(p->h[0]) || (!p->h[1]->gpu.ready && !poporon_amd_set_device(p->h[1], p->h[0]->gpu.device)) ||
+        !gpu_init(p->h[1]))
+        return false;
+    DeviceGuard dg(p->h[0]->gpu.device);
+    return prod_reserve(p, n1, n2, std::max<size_t>(1, std::min(max_blocks, prod_chunk(p, n1, n2))));
+}
+
+EXPORT bool poporon_encode_product_device(poporon_product_t *p, uint8_t *d_blocks, size_t row_pitch,
+                                          size_t block_stride, size_t row_size, size_t col_size, size_t count,
+                                          void *stream)
+{
+    const ProdCall c = {PROD_ENCODE, d_blocks, row_pitch, block_stride, row_size, col_size, count, 0, 0, 0,
+                        nullptr,     nullptr,  nullptr};
+    return prod_device(p, "poporon_encode_product_device", c, stream);
+}
+
+EXPORT bool poporon_decode_product_device(poporon_product_t *p, uint8_t *d_blocks, size_t row_pitch,
+                                          size_t block_stride, size_t row_size, size_t col_size, size_t count,
+                                          int first_axis, size_t passes, int couple, uint8_t *d_row_dirty,
+                                          uint8_t *d_col_dirty, uint8_t *d_block_ok, void *stream)
+{
+    const ProdCall c = {PROD_DECODE, d_blocks, row_pitch, block_stride, row_size,    col_size,   count,
+                        first_axis,  passes,   couple,    d_row_dirty,  d_col_dirty, d_block_ok};
+    return prod_device(p, "poporon_decode_product_device", c, stream);
+}
+
+EXPORT bool poporon_check_product_device(poporon_product_t *p, const uint8_t *d_blocks, size_t row_pitch,
+                                         size_t block_stride, size_t row_size, size_t col_size, size_t count,
+                                         uint8_t *d_row_dirty, uint8_t *d_col_dirty, uint8_t *d_block_ok, void *stream)
+{
+    const ProdCall c = {PROD_CHECK, const_cast<uint8_t *>(d_blocks), row_pitch, block_stride, row_size, col_size,
+                        count,      0, 0, 0, d_row_dirty, d_col_dirty, d_block_ok};
+    return prod_device(p, "poporon_check_product_device", c, stream);
+}
+
+/* Host forms: chunks of blocks through the row handle's first pinned slot and the device form, synchronously.
+ * Slot layout for n blocks, packed (pitch n1, stride n1 n2: the in-place row route):
+ * [blocks n1 n2 n | row flags n2 n | column flags n1 n | block ok n] */
+static const size_t kProdHostBytes = (size_t)8 << 20;
+
+static bool prod_host(poporon_product_t *p, const char *what, const ProdCall &c)
+{
+    if (!prod_args(p, what, c))
+        return false;
+    if (c.count == 0)
+        return true;
+    if (!prod_enter(p))
+        return false;
+    BatchScope bs0{p->h[0]->gpu, nullptr, true}, bs1{p->h[1]->gpu, nullptr, true};
+    DeviceGuard dg(p->h[0]->gpu.device);
+    const size_t n1 = c.k1 + p->h[0]->rs->num_roots, n2 = c.k2 + p->h[1]->rs->num_roots, bb = n1 * n2;
+    const size_t chunk = std::max<size_t>(1, std::min(c.count, kProdHostBytes / (bb + n1 + n2 + 1)));
+    const bool enc = c.op == PROD_ENCODE;
+    auto o_row = [&](size_t n) { return n * bb; };
+    auto o_col = [&](size_t n) { return o_row(n) + n * n2; };
+    auto o_ok = [&](size_t n) { return o_col(n) + n * n1; };
+    return host_chunks(
+        p->h[0], &p->h[0]->gpu.pipe[0], 1, c.count, chunk, o_ok(chunk) + chunk,
+        [&](uint8_t *hb, size_t b0, size_t n) {
+            /* an encode reads the message rectangle only */
+            const size_t rows = enc ? c.k2 : n2, cols = enc ? c.k1 : n1;
+            for (size_t b = 0; b < n; b++)
+                for (size_t i = 0; i < rows; i++)
+                    memcpy(hb + b * bb + i * n1, c.blocks + (b0 + b) * c.bstride + i * c.pitch, cols);
+        },
+        [&](GpuCtx::PipeSlot &ps, size_t n) {
+            ProdCall d = c;
+            d.blocks = ps.dev;
+            d.pitch = n1;
+            d.bstride = bb;
+            d.count = n;
+            d.row_dirty = ps.dev + o_row(n);
+            d.col_dirty = ps.dev + o_col(n);
+            d.block_ok = ps.dev + o_ok(n);
+            HIP_OK(hipMemcpyAsync(ps.dev, ps.host, n * bb, hipMemcpyHostToDevice, ps.stream));
+            if (!prod_run(p, d, ps.stream))
+                return false;
+            HIP_OK(hipMemcpyAsync(ps.host, ps.dev, enc ? n * bb : o_ok(n) + n, hipMemcpyDeviceToHost, ps.stream));
+            return true;
+        },
+        [&](const uint8_t *hb, size_t b0, size_t n) {
+            for (size_t b = 0; b < n; b++)
+                for (size_t i = 0; i < n2; i++) {
+                    /* an encode hands back parity only: the tail of a message row, the whole of a parity row */
+                    const size_t j0 = enc && i < c.k2 ? c.k1 : 0;
+                    memcpy(c.blocks + (b0 + b) * c.bstride + i * c.pitch + j0, hb + b * bb + i * n1 + j0, n1 - j0);
+                }
+            if (enc)
+                return;
+            if (c.row_dirty)
+                memcpy(c.row_dirty + b0 * n2, hb + o_row(n), n * n2);
+            if (c.col_dirty)
+                memcpy(c.col_dirty + b0 * n1, hb + o_col(n), n * n1);
+            if (c.block_ok)
+                memcpy(c.block_ok + b0, hb + o_ok(n), n);
+        },
+        "HIP failure in a product-code host batch");
+}
+
+EXPORT bool poporon_encode_product(poporon_product_t *p, uint8_t *blocks, size_t row_pitch, size_t block_stride,
+                                   size_t row_size, size_t col_size, size_t count)
+{
+    const ProdCall c = {PROD_ENCODE, blocks, row_pitch, block_stride, row_size, col_size, count, 0, 0, 0,
+                        nullptr,     nullptr, nullptr};
+    return prod_host(p, "poporon_encode_product", c);
+}
+
+EXPORT bool poporon_decode_product(poporon_product_t *p, uint8_t *blocks, size_t row_pitch, size_t block_stride,
+                                   size_t row_size, size_t col_size, size_t count, int first_axis, size_t passes,
+                                   int couple, uint8_t *row_dirty, uint8_t *col_dirty, uint8_t *block_ok)
+{
+    const ProdCall c = {PROD_DECODE, blocks, row_pitch, block_stride, row_size,  col_size, count,
+                        first_axis,  passes, couple,    row_dirty,    col_dirty, block_ok};
+    return prod_host(p, "poporon_decode_product", c);
 }
 
 /* ------------------------------------------------------------------------ */

@@ -493,6 +493,36 @@ hipError_t rsk_plane_lists(const uint32_t *lost, uint32_t lost_count, uint8_t *p
                            size_t n, hipStream_t s);
 
 /*
+ * Product-code blocks (rs_product.hip): block b is rows of bytes `pitch` apart
+ * at blocks + b*bstride.  Axis 0: codeword c of a block is its row c, symbol m
+ * its byte m; axis 1: codeword c is column c, symbol m its byte in row m.
+ * `rows` are the wire rows of the chunk (16-byte aligned): codeword (b, c),
+ * c < cw, at (b*cw + c)*w.  Only the symbols [m0, m1) of a codeword move.
+ *   rsk_prod_tile     the tile of a workgroup: g whole blocks (tpb = 1), or
+ *                     tpb tiles of u codewords per block; false for no code
+ *   rsk_prod_gather   blocks -> rows
+ *   rsk_prod_scatter  rows -> blocks
+ *   rsk_prod_lists    per block the set flags of flags[b*nf .. + nf) ascending,
+ *                     n of them: when ra/2 < n <= ra every one of the block's
+ *                     cwa codewords gets that list (zeros behind it) in `stride`
+ *                     bytes (a multiple of 16 on a 16-byte boundary) and the
+ *                     count n, else zeros and the count 0
+ *   rsk_prod_ok       ok[b] = no flag of rowf[b*n2 .. + n2), colf[b*n1 .. + n1)
+ * Nothing outside the blocks' rectangles and the chunk's rows is touched.
+ */
+#define RS_PROD_LDS 32768u      /* LDS bytes of a workgroup's tile at the most (plus 16 for its alignment) */
+#define RS_PROD_LDS_PACK 16384u /* ... of a tile of several whole blocks */
+bool rsk_prod_tile(uint32_t w, uint32_t cw, uint32_t *g, uint32_t *u, uint32_t *tpb);
+hipError_t rsk_prod_gather(const uint8_t *blocks, size_t pitch, size_t bstride, size_t count, uint32_t axis, uint32_t w,
+                           uint32_t cw, uint32_t m0, uint32_t m1, uint8_t *rows, hipStream_t s);
+hipError_t rsk_prod_scatter(const uint8_t *rows, uint8_t *blocks, size_t pitch, size_t bstride, size_t count,
+                            uint32_t axis, uint32_t w, uint32_t cw, uint32_t m0, uint32_t m1, hipStream_t s);
+hipError_t rsk_prod_lists(const uint8_t *flags, uint32_t nf, uint32_t ra, uint32_t cwa, uint8_t *pos, uint32_t stride,
+                          uint8_t *cnt, size_t nblocks, hipStream_t s);
+hipError_t rsk_prod_ok(const uint8_t *rowf, uint32_t n2, const uint8_t *colf, uint32_t n1, uint8_t *ok, size_t nblocks,
+                       hipStream_t s);
+
+/*
  * Reports and erasure lists (rs_report.hip): the sparse non-zero bytes of a
  * codeword-shaped region as an ascending list of at most nr entries per
  * codeword, the slots behind the count 0, bytes nr .. stride never written.
