@@ -124,6 +124,12 @@ struct TimedLaunch {
     hipEvent_t a, b;
 };
 
+/* a device buffer grown on demand (ensure_buf): cap counts the owner's units (codewords, list rows, bytes) */
+struct DevBuf {
+    uint8_t *p = nullptr;
+    size_t cap = 0;
+};
+
 struct GpuCtx {
     bool timing = false;
     std::vector<TimedLaunch> pending;
@@ -143,16 +149,13 @@ struct GpuCtx {
     size_t rem_cap = 0;
     /* staging rows of the interleaved calls (rs_interleave.hip), RS_ILV_ROW
      * bytes per codeword; shared across streams under rem's ordering */
-    uint8_t *ilv = nullptr;
-    size_t ilv_cap = 0;
+    DevBuf ilv;
     /* the rows before a decode, for the report calls (rs_report.hip): wire rows,
      * RS_ILV_ROW bytes per codeword allocated; ordered as ilv is */
-    uint8_t *rep = nullptr;
-    size_t rep_cap = 0;
-    /* the plane calls' erasure lists (rs_planes.hip): plist_cap rows of plane_list_stride bytes, then plist_cap
+    DevBuf rep;
+    /* the plane calls' erasure lists (rs_planes.hip): plist.cap rows of plane_list_stride bytes, then plist.cap
      * counts; ordered as ilv is */
-    uint8_t *plist = nullptr;
-    size_t plist_cap = 0;
+    DevBuf plist;
     /* the wire form's device image (RS_ILV_WIRE_BYTES, rs_device.h); wire_ok: it
      * holds the handle's form as last set (ensure_wire) */
     uint8_t *wire = nullptr;
@@ -1122,7 +1125,7 @@ static void gpu_release(GpuCtx &g)
 {
     const int dev = g.device;
     const bool any = g.ready || g.stream || g.sstream || g.tab || g.gtab || g.rem || g.ltab || g.lws || g.stage ||
-                     g.hstage || g.zc || g.ilv || g.rep || g.plist || g.wire || g.rslot.stream ||
+                     g.hstage || g.zc || g.ilv.p || g.rep.p || g.plist.p || g.wire || g.rslot.stream ||
                      g.rem_done || g.registered || g.batch_ev ||
                      g.pipe[0].stream || g.pipe[1].stream || g.pipe[2].stream;
     if (!any || dev < 0) {
@@ -1151,9 +1154,8 @@ static void gpu_release(GpuCtx &g)
     (void)hipFree(g.tab);
     (void)hipFree(g.gtab);
     (void)hipFree(g.rem);
-    (void)hipFree(g.ilv);
-    (void)hipFree(g.rep);
-    (void)hipFree(g.plist);
+    for (DevBuf *b : {&g.ilv, &g.rep, &g.plist})
+        (void)hipFree(b->p);
     (void)hipFree(g.wire);
     (void)hipFree(g.ltab);
     (void)hipFree(g.lws);
@@ -1389,6 +1391,32 @@ static bool ensure_rem(poporon_t *h, size_t count)
     HIP_OK(hipMalloc((void **)&g.rem, rs_ws_bytes(cap)));
     g.rem_cap = cap;
     return true;
+}
+
+/* b anew with cap units of unit_bytes; the caller has waited for its readers */
+static bool buf_renew(DevBuf &b, size_t cap, size_t unit_bytes)
+{
+    HIP_OK(hipFree(b.p));
+    b = DevBuf();
+    HIP_OK(hipMalloc((void **)&b.p, cap * unit_bytes));
+    b.cap = cap;
+    return true;
+}
+
+/* The handle's buffers that the layout forms share across streams under rem's
+ * ordering (ilv, rep, plist): at least `units` units of unit_bytes, min_units
+ * when it is allocated at all.  The last reader of the old buffer may run on
+ * any stream the caller chose: wait for it before the free. */
+static bool ensure_buf(GpuCtx &g, DevBuf &b, size_t units, size_t unit_bytes, size_t min_units)
+{
+    if (b.cap >= units)
+        return true;
+    if (b.p) {
+        if (g.rem_pending)
+            HIP_OK(hipEventSynchronize(g.rem_done));
+        g.rem_pending = false;
+    }
+    return buf_renew(b, std::max(units, min_units), unit_bytes);
 }
 
 static bool ensure_stage(poporon_t *h, size_t bytes)
@@ -2693,21 +2721,7 @@ EXPORT bool poporon_ldpc_decode_batch(poporon_t *h, uint8_t *data, size_t data_s
  */
 static bool ensure_ilv(poporon_t *h, size_t codewords)
 {
-    GpuCtx &g = h->gpu;
-    if (g.ilv_cap >= codewords)
-        return true;
-    const size_t cap = std::max(codewords, (size_t)RS_ILV_MAX_DEPTH);
-    if (g.ilv) {
-        if (g.rem_pending) /* its last reader may run on any stream the caller chose */
-            HIP_OK(hipEventSynchronize(g.rem_done));
-        g.rem_pending = false;
-        HIP_OK(hipFree(g.ilv));
-        g.ilv = nullptr;
-        g.ilv_cap = 0;
-    }
-    HIP_OK(hipMalloc((void **)&g.ilv, cap * RS_ILV_ROW));
-    g.ilv_cap = cap;
-    return true;
+    return ensure_buf(h->gpu, h->gpu.ilv, codewords, RS_ILV_ROW, RS_ILV_MAX_DEPTH);
 }
 
 /* The report calls' snapshot buffer (rs_report.hip): the rows of a chunk as
@@ -2717,21 +2731,56 @@ static bool ensure_ilv(poporon_t *h, size_t codewords)
  * inside it. */
 static bool ensure_rep(poporon_t *h, size_t codewords)
 {
-    GpuCtx &g = h->gpu;
-    if (g.rep_cap >= codewords)
-        return true;
-    const size_t cap = std::max(codewords, (size_t)RS_ILV_MAX_DEPTH);
-    if (g.rep) {
-        if (g.rem_pending)
-            HIP_OK(hipEventSynchronize(g.rem_done));
-        g.rem_pending = false;
-        HIP_OK(hipFree(g.rep));
-        g.rep = nullptr;
-        g.rep_cap = 0;
-    }
-    HIP_OK(hipMalloc((void **)&g.rep, cap * RS_ILV_ROW));
-    g.rep_cap = cap;
+    return ensure_buf(h->gpu, h->gpu.rep, codewords, RS_ILV_ROW, RS_ILV_MAX_DEPTH);
+}
+
+/* list rows sit on a 16-byte aligned base at a stride that is a multiple of 16: the 32-erasure kernel's fast route */
+static size_t plane_list_stride(const poporon_t *h) { return rs_ws_round16(h->rs->num_roots); }
+
+/* The plane and product calls' erasure lists (rs_planes.hip, rs_product.hip): plist.cap list rows, then plist.cap
+ * counts */
+static bool ensure_plist(poporon_t *h, size_t codewords)
+{
+    return ensure_buf(h->gpu, h->gpu.plist, codewords, plane_list_stride(h) + 1, 0);
+}
+
+/* every form's first refusals: a handle, and an RS one; then the size of its rows */
+static bool rs_handle(const poporon_t *h, const char *what)
+{
+    if (!h)
+        return fail("%s: NULL handle", what);
+    if (h->fec_type != PPLN_FEC_RS)
+        return fail("%s serves RS handles", what);
     return true;
+}
+
+static bool form_size(const poporon_t *h, const char *what, size_t size)
+{
+    return check_decode_size(h, size) || fail("%s: size %zu outside [1, %u]", what, size, (unsigned)kmax(h));
+}
+
+/* after the argument checks: run(stream) inside the batch scope on the handle's device.  A device form enqueues on
+ * the caller's stream and returns; a host form (host: no stream) returns when its work has run. */
+template <class F> static bool form_scope(poporon_t *h, size_t count, void *stream, bool host, F &&run)
+{
+    if (count == 0)
+        return true;
+    if (!batch_enter(h))
+        return false;
+    BatchScope bsc{h->gpu, (hipStream_t)stream, host};
+    DeviceGuard dg(h->gpu.device);
+    return run((hipStream_t)stream);
+}
+
+/* the reserve calls: the handle's device context, then run() on its device */
+template <class F> static bool reserve_scope(poporon_t *h, const char *what, F &&run)
+{
+    if (!h)
+        return fail("NULL handle");
+    if (!rs_handle(h, what) || !gpu_init(h))
+        return false;
+    DeviceGuard dg(h->gpu.device);
+    return run();
 }
 
 /* where a report goes: num[c], pos / val[c * stride .. + num_roots) */
@@ -2755,13 +2804,13 @@ static bool rep_snapshot(poporon_t *h, const DecodeCall &c)
     if (p == d + size && ds == w && ps == w) {
         if (t.a)
             HIP_OK(hipEventRecord(t.a, s));
-        HIP_OK(hipMemcpyAsync(g.rep, d, n * w, hipMemcpyDeviceToDevice, s));
+        HIP_OK(hipMemcpyAsync(g.rep.p, d, n * w, hipMemcpyDeviceToDevice, s));
         if (t.a) {
             HIP_OK(hipEventRecord(t.b, s));
             rs_launch_timer.n = 1;
         }
     } else {
-        HIP_OK(rsk_snapshot(d, ds, p, ps, g.rep, (uint32_t)size, nr, n, s));
+        HIP_OK(rsk_snapshot(d, ds, p, ps, g.rep.p, (uint32_t)size, nr, n, s));
     }
     t.done();
     return true;
@@ -2771,15 +2820,82 @@ static bool rep_snapshot(poporon_t *h, const DecodeCall &c)
 static bool rep_diff(poporon_t *h, const DecodeCall &c, const RepOut &o, size_t c0)
 {
     STAGE(h->gpu, POPORON_AMD_KERNEL_REPORT, c.s,
-          rsk_report(c.data, c.ds, c.par, c.ps, h->gpu.rep, (uint32_t)c.size, h->rs->num_roots, c.count, o.num + c0,
+          rsk_report(c.data, c.ds, c.par, c.ps, h->gpu.rep.p, (uint32_t)c.size, h->rs->num_roots, c.count, o.num + c0,
                      o.pos + c0 * o.stride, o.val + c0 * o.stride, o.stride, c.s));
     return true;
 }
 
-enum { ILV_ENCODE, ILV_DECODE, ILV_CHECK };
+/*
+ * The staged-chunk driver: what the interleaved, report, convolutional-check
+ * and plane calls have in common.  A call is an operation on `count` codewords,
+ * `chunk` at a time, and a layout of two callables in the manner of
+ * host_chunks: gather(c0, n, rows) says where the rows of codewords
+ * [c0, c0 + n) are, after bringing them there, and scatter(c0, n) takes them
+ * back (not called after a check).  Everything between is here and only here:
+ * the snapshot buffer of a report, the one DecodeCall of a chunk with every
+ * per-codeword array advanced by c0, snapshot / decode / diff, encode or check,
+ * and the ordering across streams of the handle's shared buffers -- a call whose
+ * rows are staged (ilv, with it plist) or that reports (rep) waits for rem_done
+ * before its first writer and records it behind its last reader; a call on the
+ * caller's own rows without a report does neither.
+ */
+enum FormOp { FORM_ENCODE, FORM_DECODE, FORM_CHECK };
+
+struct FormCall {
+    FormOp op;
+    size_t size, count, chunk; /* count, chunk: codewords */
+    bool staged;               /* the rows are the handle's staging rows (ilv), which the driver sizes */
+    const uint8_t *pos;        /* FORM_DECODE: erasure lists, per codeword or (shared_lists) one for all */
+    size_t pos_stride;
+    const uint8_t *cnt;
+    bool shared_lists;
+    uint8_t *ok, *cor;
+    uint8_t *dirty; /* FORM_CHECK: its flags; FORM_DECODE: non-NULL for a check of the decoded rows */
+    RepOut rep;     /* FORM_DECODE: the report arrays (num NULL: none) */
+};
+
+struct FormRows {
+    uint8_t *data;
+    size_t ds;
+    uint8_t *par;
+    size_t ps;
+};
+
+template <class Gather, class Scatter>
+static bool form_chunks(poporon_t *h, const FormCall &c, hipStream_t s, Gather &&gather, Scatter &&scatter)
+{
+    GpuCtx &g = h->gpu;
+    const bool report = c.op == FORM_DECODE && c.rep.num, shared = c.staged || report;
+    const size_t n0 = std::min(c.count, c.chunk);
+    if ((report && !ensure_rep(h, n0)) || (c.staged && !ensure_ilv(h, n0)) || (shared && !rem_acquire(g, s)))
+        return false;
+    for (size_t c0 = 0; c0 < c.count; c0 += c.chunk) {
+        const size_t n = std::min(c.chunk, c.count - c0), l0 = c.shared_lists ? 0 : c0;
+        FormRows r;
+        if (!gather(c0, n, r))
+            return false;
+        if (c.op == FORM_ENCODE) {
+            if (!launch_encode(h, r.data, r.ds, r.par, r.ps, c.size, n, s))
+                return false;
+        } else if (c.op == FORM_DECODE) {
+            const DecodeCall d = {.data = r.data, .ds = r.ds, .par = r.par, .ps = r.ps, .size = c.size, .count = n,
+                                  .pos8 = c.pos ? c.pos + l0 * c.pos_stride : nullptr, .pos_stride = c.pos_stride,
+                                  .cnt = c.pos ? c.cnt + l0 : nullptr, .ok = c.ok + c0,
+                                  .corrected = c.cor ? c.cor + c0 : nullptr, .s = s};
+            /* report: the rows as gathered are the snapshot */
+            if ((report && !rep_snapshot(h, d)) || !launch_decode(h, d) || (report && !rep_diff(h, d, c.rep, c0)))
+                return false;
+        }
+        if (c.op != FORM_ENCODE && c.dirty && !launch_check(h, r.data, r.ds, r.par, r.ps, c.size, n, c.dirty + c0, s))
+            return false;
+        if (c.op != FORM_CHECK && !scatter(c0, n))
+            return false;
+    }
+    return !shared || rem_release(g, s);
+}
 
 struct IlvCall {
-    int op;
+    FormOp op;
     uint8_t *data;
     size_t ds;
     uint8_t *par;
@@ -2789,7 +2905,7 @@ struct IlvCall {
     size_t pos_stride;
     const uint8_t *cnt;
     uint8_t *ok, *cor, *dirty;
-    RepOut rep; /* ILV_DECODE: the report arrays (num NULL: none) */
+    RepOut rep; /* FORM_DECODE: the report arrays (num NULL: none) */
 };
 
 static size_t ilv_chunk_frames(const poporon_t *h, size_t depth) { return std::max<size_t>(1, h->ilv_chunk / depth); }
@@ -2797,16 +2913,14 @@ static size_t ilv_chunk_frames(const poporon_t *h, size_t depth) { return std::m
 /* the checks every interleaved entry point makes before it touches the GPU */
 static bool ilv_args(const poporon_t *h, const char *what, const IlvCall &c)
 {
-    if (!h)
-        return fail("%s: NULL handle", what);
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("%s serves RS handles", what);
-    if (c.count && (!c.data || !c.par || (c.op == ILV_DECODE && !c.ok) || (c.op == ILV_CHECK && !c.dirty)))
+    if (!rs_handle(h, what))
+        return false;
+    if (c.count && (!c.data || !c.par || (c.op == FORM_DECODE && !c.ok) || (c.op == FORM_CHECK && !c.dirty)))
         return fail("%s: NULL argument", what);
     if (c.depth < 1 || c.depth > RS_ILV_MAX_DEPTH)
         return fail("%s: depth %zu outside [1, %u]", what, c.depth, (unsigned)RS_ILV_MAX_DEPTH);
-    if (!check_decode_size(h, c.size))
-        return fail("%s: size %zu outside [1, %u]", what, c.size, (unsigned)kmax(h));
+    if (!form_size(h, what, c.size))
+        return false;
     const size_t nr = h->rs->num_roots;
     if (c.ds < c.size * c.depth)
         return fail("%s: data_stride %zu < size * depth = %zu", what, c.ds, c.size * c.depth);
@@ -2850,86 +2964,64 @@ static bool ensure_wire(poporon_t *h)
 static bool ilv_run(poporon_t *h, const IlvCall &c, hipStream_t s)
 {
     GpuCtx &g = h->gpu;
-    const uint32_t nr = h->rs->num_roots;
-    const size_t cf = ilv_chunk_frames(h, c.depth);
+    const uint32_t nr = h->rs->num_roots, size = (uint32_t)c.size, depth = (uint32_t)c.depth;
     /* with a wire form every byte changes on its way in and out: depth 1 is staged too */
-    const bool mapped = h->wf_set;
-    const bool staged = c.depth > 1 || mapped;
-    const bool report = c.op == ILV_DECODE && c.rep.num;
-    if (report && !staged) /* depth 1 is the row layout: the row report */
+    const bool mapped = h->wf_set, staged = depth > 1 || mapped, decode = c.op == FORM_DECODE;
+    if (decode && c.rep.num && !staged) /* depth 1 is the row layout: the row report */
         return rep_run(h, {.data = c.data, .ds = c.ds, .par = c.par, .ps = c.ps, .size = c.size, .count = c.count,
                            .pos8 = c.pos, .pos_stride = c.pos_stride, .cnt = c.cnt, .ok = c.ok, .corrected = c.cor,
                            .s = s},
                        c.rep);
-    if (report && !ensure_rep(h, std::min(c.count, cf) * c.depth))
-        return false;
-    if (staged && (!ensure_ilv(h, std::min(c.count, cf) * c.depth) || !rem_acquire(g, s)))
-        return false;
     if (mapped && !ensure_wire(h))
         return false;
     /* an encode reads the message through to_code and uses no sequence */
-    const uint32_t xlen = c.op == ILV_ENCODE ? 0u : (uint32_t)h->wf_seq.size();
-    for (size_t f0 = 0; f0 < c.count; f0 += cf) {
-        const size_t n = std::min(cf, c.count - f0), ncw = n * c.depth, c0 = f0 * c.depth;
-        uint8_t *fd = c.data + f0 * c.ds, *fp = c.par + f0 * c.ps;
-        uint8_t *rd = staged ? g.ilv : fd, *rp = staged ? g.ilv + c.size : fp;
-        const size_t rds = staged ? c.size + nr : c.ds, rps = staged ? c.size + nr : c.ps; /* staged: wire rows */
-        if (mapped)
-            STAGE(g, POPORON_AMD_KERNEL_ILV_GATHER, s,
-                  rsk_ilv_gather_map(fd, c.ds, fp, c.ps, g.ilv, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
-                                     c.op != ILV_ENCODE, g.wire, xlen, s));
-        else if (staged)
-            STAGE(g, POPORON_AMD_KERNEL_ILV_GATHER, s,
-                  rsk_ilv_gather(fd, c.ds, fp, c.ps, g.ilv, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
-                                 c.op != ILV_ENCODE, s));
-        if (c.op == ILV_ENCODE) {
-            if (!launch_encode(h, rd, rds, rp, rps, c.size, ncw, s))
-                return false;
-        } else if (c.op == ILV_DECODE) {
-            const DecodeCall d = {.data = rd, .ds = rds, .par = rp, .ps = rps, .size = c.size, .count = ncw,
-                                  .pos8 = c.pos ? c.pos + c0 * c.pos_stride : nullptr, .pos_stride = c.pos_stride,
-                                  .cnt = c.pos ? c.cnt + c0 : nullptr, .ok = c.ok + c0,
-                                  .corrected = c.cor ? c.cor + c0 : nullptr, .s = s};
-            /* report: the staging rows as gathered are the snapshot (wire rows: one device copy) */
-            if (report && !rep_snapshot(h, d))
-                return false;
-            if (!launch_decode(h, d))
-                return false;
-            if (report && !rep_diff(h, d, c.rep, c0))
-                return false;
-        } else if (!launch_check(h, rd, rds, rp, rps, c.size, ncw, c.dirty + c0, s)) {
-            return false;
-        }
-        if (mapped && c.op != ILV_CHECK)
-            STAGE(g, POPORON_AMD_KERNEL_ILV_SCATTER, s,
-                  rsk_ilv_scatter_map(g.ilv, fd, c.ds, fp, c.ps, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
-                                      c.op == ILV_DECODE, g.wire, s));
-        else if (staged && c.op != ILV_CHECK)
-            STAGE(g, POPORON_AMD_KERNEL_ILV_SCATTER, s,
-                  rsk_ilv_scatter(g.ilv, fd, c.ds, fp, c.ps, (uint32_t)c.size, nr, (uint32_t)c.depth, n,
-                                  c.op == ILV_DECODE, s));
-    }
-    return !staged || rem_release(g, s);
+    const uint32_t xlen = c.op == FORM_ENCODE ? 0u : (uint32_t)h->wf_seq.size();
+    /* whole frames: codewords [c0, c0 + n) are frames [c0 / depth, (c0 + n) / depth) */
+    const FormCall f = {.op = c.op, .size = c.size, .count = c.count * depth,
+                        .chunk = ilv_chunk_frames(h, depth) * depth, .staged = staged, .pos = c.pos,
+                        .pos_stride = c.pos_stride, .cnt = c.cnt, .ok = c.ok, .cor = c.cor, .dirty = c.dirty,
+                        .rep = c.rep};
+    return form_chunks(
+        h, f, s,
+        [&](size_t c0, size_t n, FormRows &r) {
+            uint8_t *fd = c.data + c0 / depth * c.ds, *fp = c.par + c0 / depth * c.ps;
+            if (!staged) { /* in place: the caller's rows, and none of the handle's buffers */
+                r = {fd, c.ds, fp, c.ps};
+                return true;
+            }
+            r = {g.ilv.p, size + nr, g.ilv.p + size, size + nr}; /* wire rows */
+            if (mapped)
+                STAGE(g, POPORON_AMD_KERNEL_ILV_GATHER, s,
+                      rsk_ilv_gather_map(fd, c.ds, fp, c.ps, g.ilv.p, size, nr, depth, n / depth, c.op != FORM_ENCODE,
+                                         g.wire, xlen, s));
+            else
+                STAGE(g, POPORON_AMD_KERNEL_ILV_GATHER, s,
+                      rsk_ilv_gather(fd, c.ds, fp, c.ps, g.ilv.p, size, nr, depth, n / depth, c.op != FORM_ENCODE, s));
+            return true;
+        },
+        [&](size_t c0, size_t n) {
+            uint8_t *fd = c.data + c0 / depth * c.ds, *fp = c.par + c0 / depth * c.ps;
+            if (mapped)
+                STAGE(g, POPORON_AMD_KERNEL_ILV_SCATTER, s,
+                      rsk_ilv_scatter_map(g.ilv.p, fd, c.ds, fp, c.ps, size, nr, depth, n / depth, decode, g.wire, s));
+            else if (staged)
+                STAGE(g, POPORON_AMD_KERNEL_ILV_SCATTER, s,
+                      rsk_ilv_scatter(g.ilv.p, fd, c.ds, fp, c.ps, size, nr, depth, n / depth, decode, s));
+            return true;
+        });
 }
 
 static bool ilv_device(poporon_t *h, const char *what, const IlvCall &c, void *stream)
 {
-    if (!ilv_args(h, what, c))
-        return false;
-    if (c.count == 0)
-        return true;
-    if (!batch_enter(h))
-        return false;
-    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
-    DeviceGuard dg(h->gpu.device);
-    return ilv_run(h, c, (hipStream_t)stream);
+    return ilv_args(h, what, c) &&
+           form_scope(h, c.count, stream, false, [&](hipStream_t s) { return ilv_run(h, c, s); });
 }
 
 EXPORT bool poporon_encode_interleaved_device(poporon_t *h, const uint8_t *d_data, size_t data_stride,
                                               uint8_t *d_parity, size_t parity_stride, size_t size, size_t depth,
                                               size_t count, void *stream)
 {
-    const IlvCall c = {ILV_ENCODE, const_cast<uint8_t *>(d_data), data_stride, d_parity, parity_stride, size, depth,
+    const IlvCall c = {FORM_ENCODE, const_cast<uint8_t *>(d_data), data_stride, d_parity, parity_stride, size, depth,
                        count,      nullptr, 0, nullptr, nullptr, nullptr, nullptr};
     return ilv_device(h, "poporon_encode_interleaved_device", c, stream);
 }
@@ -2940,7 +3032,7 @@ EXPORT bool poporon_decode_interleaved_device(poporon_t *h, uint8_t *d_data, siz
                                               const uint8_t *d_counts, uint8_t *d_ok, uint8_t *d_corrected,
                                               void *stream)
 {
-    const IlvCall c = {ILV_DECODE, d_data,      data_stride,      d_parity, parity_stride, size,        depth,
+    const IlvCall c = {FORM_DECODE, d_data,      data_stride,      d_parity, parity_stride, size,        depth,
                        count,      d_positions, positions_stride, d_counts, d_ok,          d_corrected, nullptr};
     return ilv_device(h, "poporon_decode_interleaved_device", c, stream);
 }
@@ -2949,23 +3041,18 @@ EXPORT bool poporon_check_interleaved_device(poporon_t *h, const uint8_t *d_data
                                              const uint8_t *d_parity, size_t parity_stride, size_t size, size_t depth,
                                              size_t count, uint8_t *d_dirty, void *stream)
 {
-    const IlvCall c = {ILV_CHECK, const_cast<uint8_t *>(d_data), data_stride, const_cast<uint8_t *>(d_parity),
+    const IlvCall c = {FORM_CHECK, const_cast<uint8_t *>(d_data), data_stride, const_cast<uint8_t *>(d_parity),
                        parity_stride, size, depth, count, nullptr, 0, nullptr, nullptr, nullptr, d_dirty};
     return ilv_device(h, "poporon_check_interleaved_device", c, stream);
 }
 
 EXPORT bool poporon_amd_reserve_interleaved(poporon_t *h, size_t max_codewords)
 {
-    if (!h)
-        return fail("NULL handle");
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("poporon_amd_reserve_interleaved serves RS handles");
-    if (!gpu_init(h))
-        return false;
-    DeviceGuard dg(h->gpu.device);
-    /* a chunk is ilv_chunk codewords at most, or one frame where that is more */
-    const size_t n = std::min(max_codewords, std::max(h->ilv_chunk, (size_t)RS_ILV_MAX_DEPTH));
-    return ensure_ilv(h, n) && ensure_rem(h, n) && ensure_wire(h);
+    return reserve_scope(h, "poporon_amd_reserve_interleaved", [&] {
+        /* a chunk is ilv_chunk codewords at most, or one frame where that is more */
+        const size_t n = std::min(max_codewords, std::max(h->ilv_chunk, (size_t)RS_ILV_MAX_DEPTH));
+        return ensure_ilv(h, n) && ensure_rem(h, n) && ensure_wire(h);
+    });
 }
 
 /* Host forms: chunks of frames through one pinned slot and the device form,
@@ -2973,16 +3060,8 @@ EXPORT bool poporon_amd_reserve_interleaved(poporon_t *h, size_t max_codewords)
  * [frames (size + nr) depth n | to 16 | positions nr ncw | counts ncw | ok ncw | corrected ncw] */
 static const size_t kIlvHostBytes = (size_t)8 << 20;
 
-static bool ilv_host(poporon_t *h, const char *what, const IlvCall &c)
+static bool ilv_host_run(poporon_t *h, const IlvCall &c)
 {
-    if (!ilv_args(h, what, c))
-        return false;
-    if (c.count == 0)
-        return true;
-    if (!batch_enter(h))
-        return false;
-    BatchScope bsc{h->gpu, nullptr, true};
-    DeviceGuard dg(h->gpu.device);
     const size_t nr = h->rs->num_roots, db = c.size * c.depth, pb = nr * c.depth, fb = db + pb;
     const size_t eb = c.pos ? nr : 0; /* erasure slots per codeword */
     const size_t chunk = std::max<size_t>(1, std::min(c.count, kIlvHostBytes / (fb + c.depth * (eb + 3))));
@@ -2995,7 +3074,7 @@ static bool ilv_host(poporon_t *h, const char *what, const IlvCall &c)
         [&](uint8_t *hb, size_t f0, size_t n) {
             const size_t ncw = n * c.depth, c0 = f0 * c.depth;
             copy_rows(hb, fb, c.data + f0 * c.ds, c.ds, db, n);
-            if (c.op != ILV_ENCODE)
+            if (c.op != FORM_ENCODE)
                 copy_rows(hb + db, fb, c.par + f0 * c.ps, c.ps, pb, n);
             if (c.pos) {
                 copy_rows(hb + o_pos(n), nr, c.pos + c0 * c.pos_stride, c.pos_stride, nr, ncw);
@@ -3011,7 +3090,7 @@ static bool ilv_host(poporon_t *h, const char *what, const IlvCall &c)
             if (!ilv_run(h, d, ps.stream))
                 return false;
             HIP_OK(hipMemcpyAsync(ps.host, ps.dev, n * fb, hipMemcpyDeviceToHost, ps.stream));
-            if (c.op == ILV_DECODE)
+            if (c.op == FORM_DECODE)
                 HIP_OK(hipMemcpyAsync(ps.host + o_ok(n), ps.dev + o_ok(n), 2 * n * c.depth, hipMemcpyDeviceToHost,
                                       ps.stream));
             return true;
@@ -3019,7 +3098,7 @@ static bool ilv_host(poporon_t *h, const char *what, const IlvCall &c)
         [&](const uint8_t *hb, size_t f0, size_t n) {
             const size_t ncw = n * c.depth, c0 = f0 * c.depth;
             copy_rows(c.par + f0 * c.ps, c.ps, hb + db, fb, pb, n);
-            if (c.op == ILV_DECODE) {
+            if (c.op == FORM_DECODE) {
                 copy_rows(c.data + f0 * c.ds, c.ds, hb, fb, db, n);
                 memcpy(c.ok + c0, hb + o_ok(n), ncw);
                 if (c.cor)
@@ -3029,10 +3108,16 @@ static bool ilv_host(poporon_t *h, const char *what, const IlvCall &c)
         "HIP failure in an interleaved host batch");
 }
 
+static bool ilv_host(poporon_t *h, const char *what, const IlvCall &c)
+{
+    return ilv_args(h, what, c) &&
+           form_scope(h, c.count, nullptr, true, [&](hipStream_t) { return ilv_host_run(h, c); });
+}
+
 EXPORT bool poporon_encode_interleaved(poporon_t *h, const uint8_t *data, size_t data_stride, uint8_t *parity,
                                        size_t parity_stride, size_t size, size_t depth, size_t count)
 {
-    const IlvCall c = {ILV_ENCODE, const_cast<uint8_t *>(data), data_stride, parity, parity_stride, size, depth,
+    const IlvCall c = {FORM_ENCODE, const_cast<uint8_t *>(data), data_stride, parity, parity_stride, size, depth,
                        count,      nullptr, 0, nullptr, nullptr, nullptr, nullptr};
     return ilv_host(h, "poporon_encode_interleaved", c);
 }
@@ -3042,7 +3127,7 @@ EXPORT bool poporon_decode_interleaved(poporon_t *h, uint8_t *data, size_t data_
                                        const uint8_t *positions, size_t positions_stride, const uint8_t *counts,
                                        uint8_t *ok, uint8_t *corrected)
 {
-    const IlvCall c = {ILV_DECODE, data,      data_stride,      parity, parity_stride, size,      depth,
+    const IlvCall c = {FORM_DECODE, data,      data_stride,      parity, parity_stride, size,      depth,
                        count,      positions, positions_stride, counts, ok,            corrected, nullptr};
     return ilv_host(h, "poporon_decode_interleaved", c);
 }
@@ -3053,10 +3138,8 @@ EXPORT bool poporon_decode_interleaved(poporon_t *h, uint8_t *data, size_t data_
 
 static bool wire_handle(const poporon_t *h, const char *what)
 {
-    if (!h)
-        return fail("%s: NULL handle", what);
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("%s serves RS handles", what);
+    if (!rs_handle(h, what))
+        return false;
     if (h->rs->gf->symbol_size != 8)
         return fail("%s: a wire form maps bytes; the handle's symbol_size is %u, not 8", what,
                     (unsigned)h->rs->gf->symbol_size);
@@ -3189,23 +3272,15 @@ EXPORT bool poporon_amd_get_wire_form(const poporon_t *h, uint8_t to_code[256], 
  */
 static bool rep_run(poporon_t *h, const DecodeCall &c, const RepOut &o)
 {
-    GpuCtx &g = h->gpu;
-    const size_t chunk = h->rep_chunk;
-    if (!ensure_rep(h, std::min(c.count, chunk)) || !rem_acquire(g, c.s))
-        return false;
-    for (size_t c0 = 0; c0 < c.count; c0 += chunk) {
-        DecodeCall d = c; /* rows [c0, c0 + chunk) */
-        d.count = std::min(chunk, c.count - c0);
-        d.data += c0 * c.ds;
-        d.par += c0 * c.ps;
-        d.pos8 = c.pos8 ? c.pos8 + c0 * c.pos_stride : nullptr;
-        d.cnt = c.pos8 ? c.cnt + c0 : nullptr;
-        d.ok += c0;
-        d.corrected = c.corrected ? c.corrected + c0 : nullptr;
-        if (!rep_snapshot(h, d) || !launch_decode(h, d) || !rep_diff(h, d, o, c0))
-            return false;
-    }
-    return rem_release(g, c.s);
+    const FormCall f = {.op = FORM_DECODE, .size = c.size, .count = c.count, .chunk = h->rep_chunk, .pos = c.pos8,
+                        .pos_stride = c.pos_stride, .cnt = c.cnt, .ok = c.ok, .cor = c.corrected, .rep = o};
+    return form_chunks(
+        h, f, c.s,
+        [&](size_t c0, size_t, FormRows &r) { /* the degenerate layout: the rows are where they are */
+            r = {c.data + c0 * c.ds, c.ds, c.par + c0 * c.ps, c.ps};
+            return true;
+        },
+        [](size_t, size_t) { return true; });
 }
 
 /* what every report entry point checks about the report arrays */
@@ -3230,16 +3305,12 @@ EXPORT bool poporon_decode_batch_report_device(poporon_t *h, uint8_t *d_data, si
     if (!decode_row_args(h, what, true, d_data, d_parity, size, count, d_positions, positions_stride, d_counts, d_ok) ||
         !rep_args(h, what, count, o))
         return false;
-    if (count == 0)
-        return true;
-    if (!batch_enter(h))
-        return false;
-    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
-    DeviceGuard dg(h->gpu.device);
-    return rep_run(h, {.data = d_data, .ds = data_stride, .par = d_parity, .ps = parity_stride, .size = size,
-                       .count = count, .pos8 = d_positions, .pos_stride = positions_stride, .cnt = d_counts,
-                       .ok = d_ok, .corrected = d_corrected, .s = (hipStream_t)stream},
-                   o);
+    return form_scope(h, count, stream, false, [&](hipStream_t s) {
+        return rep_run(h, {.data = d_data, .ds = data_stride, .par = d_parity, .ps = parity_stride, .size = size,
+                           .count = count, .pos8 = d_positions, .pos_stride = positions_stride, .cnt = d_counts,
+                           .ok = d_ok, .corrected = d_corrected, .s = s},
+                       o);
+    });
 }
 
 EXPORT bool poporon_decode_interleaved_report_device(poporon_t *h, uint8_t *d_data, size_t data_stride,
@@ -3250,7 +3321,7 @@ EXPORT bool poporon_decode_interleaved_report_device(poporon_t *h, uint8_t *d_da
                                                      uint8_t *d_err_val, size_t report_stride, void *stream)
 {
     const char *what = "poporon_decode_interleaved_report_device";
-    const IlvCall c = {ILV_DECODE,  d_data,           data_stride, d_parity, parity_stride, size,
+    const IlvCall c = {FORM_DECODE,  d_data,           data_stride, d_parity, parity_stride, size,
                        depth,       count,            d_positions, positions_stride,        d_counts,
                        d_ok,        d_corrected,      nullptr,     {d_err_num, d_err_pos, d_err_val, report_stride}};
     if (!ilv_args(h, what, c) || !rep_args(h, what, count, c.rep))
@@ -3260,15 +3331,10 @@ EXPORT bool poporon_decode_interleaved_report_device(poporon_t *h, uint8_t *d_da
 
 EXPORT bool poporon_amd_reserve_report(poporon_t *h, size_t max_codewords)
 {
-    if (!h)
-        return fail("NULL handle");
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("poporon_amd_reserve_report serves RS handles");
-    if (!gpu_init(h))
-        return false;
-    DeviceGuard dg(h->gpu.device);
-    const size_t n = std::min(max_codewords, h->rep_chunk);
-    return ensure_rep(h, n) && ensure_rem(h, n);
+    return reserve_scope(h, "poporon_amd_reserve_report", [&] {
+        const size_t n = std::min(max_codewords, h->rep_chunk);
+        return ensure_rep(h, n) && ensure_rem(h, n);
+    });
 }
 
 /* ------------------------------------------------------------------------ */
@@ -3324,10 +3390,8 @@ EXPORT size_t poporon_amd_conv_tile(size_t row_bytes, size_t branches, size_t ce
 /* the checks every convolutional entry point makes before it touches the GPU */
 static bool conv_args(const poporon_t *h, const char *what, const ConvCall &c)
 {
-    if (!h)
-        return fail("%s: NULL handle", what);
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("%s serves RS handles", what);
+    if (!rs_handle(h, what))
+        return false;
     if (c.count && (!c.stream || (c.need_rows && !c.data) || (c.need_parity && !c.par)))
         return fail("%s: NULL argument", what);
     if (c.branches < 1 || c.branches > RS_CONV_MAX_BRANCHES)
@@ -3336,8 +3400,8 @@ static bool conv_args(const poporon_t *h, const char *what, const ConvCall &c)
         return fail("%s: cell %zu outside [1, %u]", what, c.cell, (unsigned)RS_CONV_MAX_CELL);
     if (c.phase >= c.branches)
         return fail("%s: phase %zu >= branches %zu", what, c.phase, c.branches);
-    if (!check_decode_size(h, c.size))
-        return fail("%s: size %zu outside [1, %u]", what, c.size, (unsigned)kmax(h));
+    if (!form_size(h, what, c.size))
+        return false;
     const size_t nr = h->rs->num_roots;
     if (c.need_rows && c.ds < c.size)
         return fail("%s: data_stride %zu < size %zu", what, c.ds, c.size);
@@ -3370,18 +3434,6 @@ static bool conv_scatter(poporon_t *h, const ConvCall &c, hipStream_t s)
     return true;
 }
 
-/* after the argument checks: run(stream) inside the batch scope on the handle's device */
-template <class F> static bool conv_device(poporon_t *h, const ConvCall &c, void *stream, F &&run)
-{
-    if (c.count == 0)
-        return true;
-    if (!batch_enter(h))
-        return false;
-    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
-    DeviceGuard dg(h->gpu.device);
-    return run((hipStream_t)stream);
-}
-
 EXPORT bool poporon_amd_conv_interleave_device(poporon_t *h, const uint8_t *d_data, size_t data_stride,
                                                const uint8_t *d_parity, size_t parity_stride, size_t size,
                                                size_t count, size_t branches, size_t cell, size_t phase,
@@ -3390,7 +3442,7 @@ EXPORT bool poporon_amd_conv_interleave_device(poporon_t *h, const uint8_t *d_da
     const ConvCall c = {d_stream, branches, cell, phase, const_cast<uint8_t *>(d_data), data_stride,
                         const_cast<uint8_t *>(d_parity), parity_stride, size, count, true, false};
     return conv_args(h, "poporon_amd_conv_interleave_device", c) &&
-           conv_device(h, c, stream, [&](hipStream_t s) { return conv_scatter(h, c, s); });
+           form_scope(h, c.count, stream, false, [&](hipStream_t s) { return conv_scatter(h, c, s); });
 }
 
 EXPORT bool poporon_amd_conv_deinterleave_device(poporon_t *h, const uint8_t *d_stream, size_t branches, size_t cell,
@@ -3400,7 +3452,7 @@ EXPORT bool poporon_amd_conv_deinterleave_device(poporon_t *h, const uint8_t *d_
     const ConvCall c = {const_cast<uint8_t *>(d_stream), branches, cell, phase, d_data, data_stride, d_parity,
                         parity_stride, size, count, true, false};
     return conv_args(h, "poporon_amd_conv_deinterleave_device", c) &&
-           conv_device(h, c, stream, [&](hipStream_t s) { return conv_gather(h, c, s); });
+           form_scope(h, c.count, stream, false, [&](hipStream_t s) { return conv_gather(h, c, s); });
 }
 
 EXPORT bool poporon_encode_conv_device(poporon_t *h, const uint8_t *d_data, size_t data_stride, uint8_t *d_parity,
@@ -3409,7 +3461,7 @@ EXPORT bool poporon_encode_conv_device(poporon_t *h, const uint8_t *d_data, size
 {
     const ConvCall c = {d_stream, branches, cell, phase, const_cast<uint8_t *>(d_data), data_stride, d_parity,
                         parity_stride, size, count, true, true};
-    return conv_args(h, "poporon_encode_conv_device", c) && conv_device(h, c, stream, [&](hipStream_t s) {
+    return conv_args(h, "poporon_encode_conv_device", c) && form_scope(h, c.count, stream, false, [&](hipStream_t s) {
                return launch_encode(h, c.data, c.ds, c.par, c.ps, c.size, c.count, s) && conv_scatter(h, c, s);
            });
 }
@@ -3423,7 +3475,7 @@ static bool conv_decode(poporon_t *h, const char *what, const ConvCall &c, const
         !decode_row_args(h, what, true, c.data, c.par, c.size, c.count, d_positions, positions_stride, d_counts, d_ok) ||
         (rep && !rep_args(h, what, c.count, *rep)))
         return false;
-    return conv_device(h, c, stream, [&](hipStream_t s) {
+    return form_scope(h, c.count, stream, false, [&](hipStream_t s) {
         const DecodeCall d = {.data = c.data, .ds = c.ds, .par = c.par, .ps = c.ps, .size = c.size, .count = c.count,
                               .pos8 = d_positions, .pos_stride = positions_stride, .cnt = d_counts, .ok = d_ok,
                               .corrected = d_corrected, .s = s};
@@ -3468,20 +3520,20 @@ EXPORT bool poporon_check_conv_device(poporon_t *h, const uint8_t *d_stream, siz
         return false;
     if (count && !d_dirty)
         return fail("%s: NULL argument", what);
-    return conv_device(h, c, stream, [&](hipStream_t s) {
-        GpuCtx &g = h->gpu;
-        const size_t chunk = h->ilv_chunk, w = size + h->rs->num_roots;
-        if (!ensure_ilv(h, std::min(count, chunk)) || !rem_acquire(g, s))
-            return false;
-        /* chunk k is its own window of the stream: base + c0*W, phase (phase + c0*W) mod branches */
-        for (size_t c0 = 0; c0 < count; c0 += chunk) {
-            const size_t n = std::min(chunk, count - c0);
-            const ConvCall k = {c.stream + c0 * w, branches, cell, (phase + c0 * w % branches) % branches, g.ilv, w,
-                                g.ilv + size, w, size, n, true, true};
-            if (!conv_gather(h, k, s) || !launch_check(h, k.data, w, k.par, w, size, n, d_dirty + c0, s))
-                return false;
-        }
-        return rem_release(g, s);
+    return form_scope(h, c.count, stream, false, [&](hipStream_t s) {
+        const size_t w = size + h->rs->num_roots;
+        const FormCall f = {.op = FORM_CHECK, .size = size, .count = count, .chunk = h->ilv_chunk, .staged = true,
+                            .dirty = d_dirty};
+        return form_chunks(
+            h, f, s,
+            [&](size_t c0, size_t n, FormRows &r) {
+                /* chunk k is its own window of the stream: base + c0*W, phase (phase + c0*W) mod branches */
+                r = {h->gpu.ilv.p, w, h->gpu.ilv.p + size, w};
+                const ConvCall k = {c.stream + c0 * w, branches, cell, (phase + c0 * w % branches) % branches,
+                                    r.data, w, r.par, w, size, n, true, true};
+                return conv_gather(h, k, s);
+            },
+            [](size_t, size_t) { return true; });
     });
 }
 
@@ -3491,57 +3543,31 @@ EXPORT bool poporon_check_conv_device(poporon_t *h, const uint8_t *d_stream, siz
 
 /*
  * A stripe is W = size + num_roots planes, codeword c's symbol j at
- * planes[j][c] (poporon_amd.h).  plane_run mirrors ilv_run: per chunk of at
- * most ilv_chunk codewords the planes are gathered into the staging rows of
- * the interleaved calls (rs_planes.hip), the row launchers run there, routed
- * by the chunk's count, and the rows are scattered back -- the parity planes
- * after an encode, every non-NULL plane after a decode, nothing after a check.
- * The table and the lost set go to the kernels by value.  A rebuild gives every
- * codeword the same erasure list; the row decoders take per-codeword lists, so
- * the handle owns a list buffer for one chunk, filled once per call.
+ * planes[j][c] (poporon_amd.h).  plane_run is a layout of the staged-chunk
+ * driver (form_chunks): per chunk of at most ilv_chunk codewords the planes are
+ * gathered into the staging rows of the interleaved calls (rs_planes.hip), the
+ * row launchers run there, routed by the chunk's count, and the rows are
+ * scattered back -- the parity planes after an encode, every non-NULL plane
+ * after a decode, nothing after a check.  The table and the lost set go to the
+ * kernels by value.  A rebuild gives every codeword the same erasure list; the
+ * row decoders take per-codeword lists, so the handle owns a list buffer for one
+ * chunk, filled once per call.
  */
-enum { PLANE_ENCODE, PLANE_DECODE, PLANE_CHECK };
-
 struct PlaneCall {
-    int op;
+    FormOp op;
     uint8_t *const *planes; /* host array of size + num_roots device pointers */
     size_t size, count;
     const uint8_t *lost; /* host array */
     size_t lost_count;
     uint8_t *ok, *cor, *dirty;
-    RepOut rep; /* PLANE_DECODE: the report arrays (num NULL: none) */
+    RepOut rep; /* FORM_DECODE: the report arrays (num NULL: none) */
 };
-
-/* list rows sit on a 16-byte aligned base at a stride that is a multiple of 16: the 32-erasure kernel's fast route */
-static size_t plane_list_stride(const poporon_t *h) { return rs_ws_round16(h->rs->num_roots); }
-
-static bool ensure_plist(poporon_t *h, size_t codewords)
-{
-    GpuCtx &g = h->gpu;
-    if (g.plist_cap >= codewords)
-        return true;
-    if (g.plist) {
-        if (g.rem_pending)
-            HIP_OK(hipEventSynchronize(g.rem_done));
-        g.rem_pending = false;
-        HIP_OK(hipFree(g.plist));
-        g.plist = nullptr;
-        g.plist_cap = 0;
-    }
-    HIP_OK(hipMalloc((void **)&g.plist, codewords * (plane_list_stride(h) + 1)));
-    g.plist_cap = codewords;
-    return true;
-}
 
 /* the checks every plane entry point makes before it touches the GPU */
 static bool plane_args(const poporon_t *h, const char *what, const PlaneCall &c)
 {
-    if (!h)
-        return fail("%s: NULL handle", what);
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("%s serves RS handles", what);
-    if (!check_decode_size(h, c.size))
-        return fail("%s: size %zu outside [1, %u]", what, c.size, (unsigned)kmax(h));
+    if (!rs_handle(h, what) || !form_size(h, what, c.size))
+        return false;
     const size_t nr = h->rs->num_roots, w = c.size + nr;
     if (c.lost_count > nr)
         return fail("%s: lost_count %zu > num_roots (%zu)", what, c.lost_count, nr);
@@ -3555,18 +3581,18 @@ static bool plane_args(const poporon_t *h, const char *what, const PlaneCall &c)
     }
     if (c.count == 0)
         return true;
-    if (!c.planes || (c.op == PLANE_DECODE && !c.ok) || (c.op == PLANE_CHECK && !c.dirty))
+    if (!c.planes || (c.op == FORM_DECODE && !c.ok) || (c.op == FORM_CHECK && !c.dirty))
         return fail("%s: NULL argument", what);
     size_t k = 0, delivered = 0;
     for (size_t j = 0; j < w; j++) {
         const bool is_lost = k < c.lost_count && c.lost[k] == j;
         k += is_lost;
-        if (c.op == PLANE_ENCODE && j >= c.size)
+        if (c.op == FORM_ENCODE && j >= c.size)
             delivered += c.planes[j] != nullptr;
         else if (!c.planes[j] && !is_lost)
             return fail("%s: NULL plane %zu", what, j);
     }
-    if (c.op == PLANE_ENCODE && !delivered)
+    if (c.op == FORM_ENCODE && !delivered)
         return fail("%s: every parity plane is NULL", what);
     return true;
 }
@@ -3577,72 +3603,47 @@ static bool plane_run(poporon_t *h, const PlaneCall &c, hipStream_t s)
     GpuCtx &g = h->gpu;
     const uint32_t nr = h->rs->num_roots, size = (uint32_t)c.size, w = size + nr;
     const size_t chunk = h->ilv_chunk, n0 = std::min(c.count, chunk), ls = plane_list_stride(h);
-    const bool report = c.op == PLANE_DECODE && c.rep.num;
     uint32_t lost[8] = {};
     for (size_t k = 0; k < c.lost_count; k++)
         lost[c.lost[k] >> 5] |= 1u << (c.lost[k] & 31u);
     /* the planes a pass touches: the message on the way into an encode, all of them otherwise; on the way out
      * the parity of an encode, all of a decode */
-    const uint32_t gfirst = 0, glast = c.op == PLANE_ENCODE ? size : w;
-    const uint32_t sfirst = c.op == PLANE_ENCODE ? size : 0, slast = w;
+    const uint32_t gfirst = 0, glast = c.op == FORM_ENCODE ? size : w;
+    const uint32_t sfirst = c.op == FORM_ENCODE ? size : 0, slast = w;
     uintptr_t low = 0; /* every entry a multiple of 16: the kernels whose plane runs are whole slots */
     for (uint32_t j = 0; j < w; j++)
         low |= reinterpret_cast<uintptr_t>(c.planes[j]);
-    if (report && !ensure_rep(h, n0))
-        return false;
     if (c.lost_count && !ensure_plist(h, n0))
         return false;
-    if (!ensure_ilv(h, n0) || !rem_acquire(g, s))
-        return false;
-    uint8_t *rows = g.ilv;
-    for (size_t c0 = 0; c0 < c.count; c0 += chunk) {
-        const size_t n = std::min(chunk, c.count - c0);
-        const bool aligned = ((low | c0) & 15u) == 0;
-        {
+    /* one list, filled inside the first chunk's gather, serves every chunk; a decode with d_dirty checks its rows */
+    const FormCall f = {.op = c.op, .size = size, .count = c.count, .chunk = h->ilv_chunk, .staged = true,
+                        .pos = c.lost_count ? g.plist.p : nullptr, .pos_stride = ls,
+                        .cnt = c.lost_count ? g.plist.p + g.plist.cap * ls : nullptr, .shared_lists = true, .ok = c.ok,
+                        .cor = c.cor, .dirty = c.dirty, .rep = c.rep};
+    return form_chunks(
+        h, f, s,
+        [&](size_t c0, size_t n, FormRows &r) {
+            r = {g.ilv.p, w, g.ilv.p + size, w};
             KernelTimer t(g, POPORON_AMD_KERNEL_PLANE_GATHER, s);
-            if (c0 == 0 && c.lost_count) /* one list serves every chunk */
-                HIP_OK(rsk_plane_lists(lost, (uint32_t)c.lost_count, g.plist, (uint32_t)ls, g.plist + g.plist_cap * ls,
-                                       n0, s));
-            HIP_OK(rsk_plane_gather(c.planes, lost, w, gfirst, glast, c0, rows, n, aligned, s));
+            if (c0 == 0 && c.lost_count)
+                HIP_OK(rsk_plane_lists(lost, (uint32_t)c.lost_count, g.plist.p, (uint32_t)ls,
+                                       g.plist.p + g.plist.cap * ls, n0, s));
+            HIP_OK(rsk_plane_gather(c.planes, lost, w, gfirst, glast, c0, r.data, n, ((low | c0) & 15u) == 0, s));
             t.done();
-        }
-        if (c.op == PLANE_ENCODE) {
-            if (!launch_encode(h, rows, w, rows + size, w, size, n, s))
-                return false;
-        } else if (c.op == PLANE_DECODE) {
-            const DecodeCall d = {.data = rows, .ds = w, .par = rows + size, .ps = w, .size = size, .count = n,
-                                  .pos8 = c.lost_count ? g.plist : nullptr, .pos_stride = ls,
-                                  .cnt = c.lost_count ? g.plist + g.plist_cap * ls : nullptr, .ok = c.ok + c0,
-                                  .corrected = c.cor ? c.cor + c0 : nullptr, .s = s};
-            if (report && !rep_snapshot(h, d))
-                return false;
-            if (!launch_decode(h, d))
-                return false;
-            if (report && !rep_diff(h, d, c.rep, c0))
-                return false;
-            if (c.dirty && !launch_check(h, rows, w, rows + size, w, size, n, c.dirty + c0, s))
-                return false;
-        } else if (!launch_check(h, rows, w, rows + size, w, size, n, c.dirty + c0, s)) {
-            return false;
-        }
-        if (c.op != PLANE_CHECK)
+            return true;
+        },
+        [&](size_t c0, size_t n) {
             STAGE(g, POPORON_AMD_KERNEL_PLANE_SCATTER, s,
-                  rsk_plane_scatter(rows, c.planes, w, sfirst, slast, c0, n, aligned, s));
-    }
-    return rem_release(g, s);
+                  rsk_plane_scatter(g.ilv.p, c.planes, w, sfirst, slast, c0, n, ((low | c0) & 15u) == 0, s));
+            return true;
+        });
 }
 
 static bool plane_device(poporon_t *h, const char *what, const PlaneCall &c, void *stream)
 {
     if (!plane_args(h, what, c) || (c.rep.num && !rep_args(h, what, c.count, c.rep)))
         return false;
-    if (c.count == 0)
-        return true;
-    if (!batch_enter(h))
-        return false;
-    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
-    DeviceGuard dg(h->gpu.device);
-    return plane_run(h, c, (hipStream_t)stream);
+    return form_scope(h, c.count, stream, false, [&](hipStream_t s) { return plane_run(h, c, s); });
 }
 
 EXPORT size_t poporon_amd_plane_tile(size_t row_bytes)
@@ -3652,20 +3653,15 @@ EXPORT size_t poporon_amd_plane_tile(size_t row_bytes)
 
 EXPORT bool poporon_amd_reserve_planes(poporon_t *h, size_t max_codewords)
 {
-    if (!h)
-        return fail("NULL handle");
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("poporon_amd_reserve_planes serves RS handles");
-    if (!gpu_init(h))
-        return false;
-    DeviceGuard dg(h->gpu.device);
-    const size_t n = std::min(max_codewords, h->ilv_chunk);
-    return ensure_plist(h, n) && ensure_ilv(h, n) && ensure_rem(h, n);
+    return reserve_scope(h, "poporon_amd_reserve_planes", [&] {
+        const size_t n = std::min(max_codewords, h->ilv_chunk);
+        return ensure_plist(h, n) && ensure_ilv(h, n) && ensure_rem(h, n);
+    });
 }
 
 EXPORT bool poporon_encode_planes_device(poporon_t *h, uint8_t *const *planes, size_t size, size_t count, void *stream)
 {
-    const PlaneCall c = {PLANE_ENCODE, planes, size, count, nullptr, 0, nullptr, nullptr, nullptr, {}};
+    const PlaneCall c = {FORM_ENCODE, planes, size, count, nullptr, 0, nullptr, nullptr, nullptr, {}};
     return plane_device(h, "poporon_encode_planes_device", c, stream);
 }
 
@@ -3673,7 +3669,7 @@ EXPORT bool poporon_decode_planes_device(poporon_t *h, uint8_t *const *planes, s
                                          const uint8_t *lost, size_t lost_count, uint8_t *d_ok, uint8_t *d_corrected,
                                          uint8_t *d_dirty, void *stream)
 {
-    const PlaneCall c = {PLANE_DECODE, planes, size, count, lost, lost_count, d_ok, d_corrected, d_dirty, {}};
+    const PlaneCall c = {FORM_DECODE, planes, size, count, lost, lost_count, d_ok, d_corrected, d_dirty, {}};
     return plane_device(h, "poporon_decode_planes_device", c, stream);
 }
 
@@ -3684,7 +3680,7 @@ EXPORT bool poporon_decode_planes_report_device(poporon_t *h, uint8_t *const *pl
                                                 void *stream)
 {
     const char *what = "poporon_decode_planes_report_device";
-    const PlaneCall c = {PLANE_DECODE, planes, size, count, lost, lost_count, d_ok, d_corrected, d_dirty,
+    const PlaneCall c = {FORM_DECODE, planes, size, count, lost, lost_count, d_ok, d_corrected, d_dirty,
                          {d_err_num, d_err_pos, d_err_val, report_stride}};
     /* the plain call is the one without report arrays: here they are required */
     if (h && h->fec_type == PPLN_FEC_RS && !rep_args(h, what, count, c.rep))
@@ -3695,43 +3691,37 @@ EXPORT bool poporon_decode_planes_report_device(poporon_t *h, uint8_t *const *pl
 EXPORT bool poporon_check_planes_device(poporon_t *h, const uint8_t *const *planes, size_t size, size_t count,
                                         uint8_t *d_dirty, void *stream)
 {
-    const PlaneCall c = {PLANE_CHECK, const_cast<uint8_t *const *>(planes), size, count, nullptr, 0, nullptr, nullptr,
+    const PlaneCall c = {FORM_CHECK, const_cast<uint8_t *const *>(planes), size, count, nullptr, 0, nullptr, nullptr,
                          d_dirty, {}};
     return plane_device(h, "poporon_check_planes_device", c, stream);
 }
 
 /* The strided forms: one buffer, message plane j at d_data + j*data_plane_stride, parity plane p at d_parity +
  * p*parity_plane_stride.  They fill a table on the host and take the table forms' path. */
-static bool plane_table(const poporon_t *h, const char *what, size_t size, size_t count, const uint8_t *d_data,
-                        size_t ds, const uint8_t *d_parity, size_t ps, std::vector<uint8_t *> &tab)
+static bool plane_strided(poporon_t *h, const char *what, PlaneCall c, const uint8_t *d_data, size_t ds,
+                          const uint8_t *d_parity, size_t ps, void *stream)
 {
-    if (!h)
-        return fail("%s: NULL handle", what);
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("%s serves RS handles", what);
-    if (!check_decode_size(h, size))
-        return fail("%s: size %zu outside [1, %u]", what, size, (unsigned)kmax(h));
-    if (count && (!d_data || !d_parity))
+    if (!rs_handle(h, what) || !form_size(h, what, c.size))
+        return false;
+    if (c.count && (!d_data || !d_parity))
         return fail("%s: NULL argument", what);
     const size_t nr = h->rs->num_roots;
-    tab.resize(size + nr);
-    for (size_t j = 0; j < size; j++)
+    std::vector<uint8_t *> tab(c.size + nr);
+    for (size_t j = 0; j < c.size; j++)
         tab[j] = const_cast<uint8_t *>(d_data) + j * ds;
     for (size_t p = 0; p < nr; p++)
-        tab[size + p] = const_cast<uint8_t *>(d_parity) + p * ps;
-    return true;
+        tab[c.size + p] = const_cast<uint8_t *>(d_parity) + p * ps;
+    c.planes = tab.data();
+    return plane_device(h, what, c, stream);
 }
 
 EXPORT bool poporon_encode_planes_strided_device(poporon_t *h, const uint8_t *d_data, size_t data_plane_stride,
                                                  uint8_t *d_parity, size_t parity_plane_stride, size_t size,
                                                  size_t count, void *stream)
 {
-    const char *what = "poporon_encode_planes_strided_device";
-    std::vector<uint8_t *> tab;
-    if (!plane_table(h, what, size, count, d_data, data_plane_stride, d_parity, parity_plane_stride, tab))
-        return false;
-    const PlaneCall c = {PLANE_ENCODE, tab.data(), size, count, nullptr, 0, nullptr, nullptr, nullptr, {}};
-    return plane_device(h, what, c, stream);
+    const PlaneCall c = {FORM_ENCODE, nullptr, size, count, nullptr, 0, nullptr, nullptr, nullptr, {}};
+    return plane_strided(h, "poporon_encode_planes_strided_device", c, d_data, data_plane_stride, d_parity,
+                         parity_plane_stride, stream);
 }
 
 EXPORT bool poporon_decode_planes_strided_device(poporon_t *h, uint8_t *d_data, size_t data_plane_stride,
@@ -3739,24 +3729,18 @@ EXPORT bool poporon_decode_planes_strided_device(poporon_t *h, uint8_t *d_data, 
                                                  size_t count, const uint8_t *lost, size_t lost_count, uint8_t *d_ok,
                                                  uint8_t *d_corrected, uint8_t *d_dirty, void *stream)
 {
-    const char *what = "poporon_decode_planes_strided_device";
-    std::vector<uint8_t *> tab;
-    if (!plane_table(h, what, size, count, d_data, data_plane_stride, d_parity, parity_plane_stride, tab))
-        return false;
-    const PlaneCall c = {PLANE_DECODE, tab.data(), size, count, lost, lost_count, d_ok, d_corrected, d_dirty, {}};
-    return plane_device(h, what, c, stream);
+    const PlaneCall c = {FORM_DECODE, nullptr, size, count, lost, lost_count, d_ok, d_corrected, d_dirty, {}};
+    return plane_strided(h, "poporon_decode_planes_strided_device", c, d_data, data_plane_stride, d_parity,
+                         parity_plane_stride, stream);
 }
 
 EXPORT bool poporon_check_planes_strided_device(poporon_t *h, const uint8_t *d_data, size_t data_plane_stride,
                                                 const uint8_t *d_parity, size_t parity_plane_stride, size_t size,
                                                 size_t count, uint8_t *d_dirty, void *stream)
 {
-    const char *what = "poporon_check_planes_strided_device";
-    std::vector<uint8_t *> tab;
-    if (!plane_table(h, what, size, count, d_data, data_plane_stride, d_parity, parity_plane_stride, tab))
-        return false;
-    const PlaneCall c = {PLANE_CHECK, tab.data(), size, count, nullptr, 0, nullptr, nullptr, d_dirty, {}};
-    return plane_device(h, what, c, stream);
+    const PlaneCall c = {FORM_CHECK, nullptr, size, count, nullptr, 0, nullptr, nullptr, d_dirty, {}};
+    return plane_strided(h, "poporon_check_planes_strided_device", c, d_data, data_plane_stride, d_parity,
+                         parity_plane_stride, stream);
 }
 
 /* Host form: chunks of rows through one pinned slot of its own and the device
@@ -3835,38 +3819,31 @@ EXPORT bool poporon_amd_erasures_from_mask_device(poporon_t *h, const uint8_t *d
                                                   void *stream)
 {
     const char *what = "poporon_amd_erasures_from_mask_device";
-    if (!h)
-        return fail("%s: NULL handle", what);
-    if (h->fec_type != PPLN_FEC_RS)
-        return fail("%s serves RS handles", what);
+    if (!rs_handle(h, what))
+        return false;
     if (count && (!d_mask || !d_positions || !d_counts))
         return fail("%s: NULL argument", what);
     if (depth < 1 || depth > RS_ILV_MAX_DEPTH)
         return fail("%s: depth %zu outside [1, %u]", what, depth, (unsigned)RS_ILV_MAX_DEPTH);
-    if (!check_decode_size(h, size))
-        return fail("%s: size %zu outside [1, %u]", what, size, (unsigned)kmax(h));
+    if (!form_size(h, what, size))
+        return false;
     const uint32_t nr = h->rs->num_roots;
     if (mask_stride < size * depth)
         return fail("%s: mask_stride %zu < size * depth = %zu", what, mask_stride, size * depth);
     if (positions_stride < nr)
         return fail("%s: positions_stride %zu < num_roots (%u)", what, positions_stride, (unsigned)nr);
-    if (count == 0)
+    return form_scope(h, count, stream, false, [&](hipStream_t s) {
+        const size_t step = (size_t)1 << 24; /* frames per launch: frames * depth stays below 2^31 */
+        for (size_t f0 = 0; f0 < count; f0 += step) {
+            const size_t n = std::min(step, count - f0), c0 = f0 * depth;
+            KernelTimer t(h->gpu, POPORON_AMD_KERNEL_MASK_LISTS, s);
+            HIP_OK(rsk_mask_lists(d_mask + f0 * mask_stride, mask_stride, (uint32_t)size, (uint32_t)depth, nr, n,
+                                  d_positions + c0 * positions_stride, positions_stride, d_counts + c0,
+                                  d_over ? d_over + c0 : nullptr, s));
+            t.done();
+        }
         return true;
-    if (!batch_enter(h))
-        return false;
-    BatchScope bsc{h->gpu, (hipStream_t)stream, false};
-    DeviceGuard dg(h->gpu.device);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t step = (size_t)1 << 24; /* frames per launch: frames * depth stays below 2^31 */
-    for (size_t f0 = 0; f0 < count; f0 += step) {
-        const size_t n = std::min(step, count - f0), c0 = f0 * depth;
-        KernelTimer t(h->gpu, POPORON_AMD_KERNEL_MASK_LISTS, s);
-        HIP_OK(rsk_mask_lists(d_mask + f0 * mask_stride, mask_stride, (uint32_t)size, (uint32_t)depth, nr, n,
-                              d_positions + c0 * positions_stride, positions_stride, d_counts + c0,
-                              d_over ? d_over + c0 : nullptr, s));
-        t.done();
-    }
-    return true;
+    });
 }
 
 /* ------------------------------------------------------------------------ */
@@ -3876,7 +3853,8 @@ EXPORT bool poporon_amd_erasures_from_mask_device(poporon_t *h, const uint8_t *d
 /*
  * A block is a codeword of the row code along every row and of the column code
  * along every column (poporon_amd.h).  poporon_product_t owns one handle per
- * axis on one device.  prod_run mirrors plane_run: per chunk of whole blocks,
+ * axis on one device.  prod_run keeps a chunk loop of its own (two handles and
+ * alternating axes are not form_chunks' loop): per chunk of whole blocks,
  * at most ilv_chunk codewords of either axis, the whole schedule is enqueued
  * -- per pass the erasure lists from the other axis's flags (rs_prod_lists_k),
  * the axis's codewords gathered into its handle's staging rows
@@ -3889,14 +3867,11 @@ EXPORT bool poporon_amd_erasures_from_mask_device(poporon_t *h, const uint8_t *d
  */
 struct _poporon_product_t {
     poporon_t *h[2]; /* 0: the row code, 1: the column code */
-    uint8_t *ws;     /* device: [row flags n2 nb | column flags n1 nb | ok max(n1, n2) nb] of one chunk */
-    size_t ws_bytes;
+    DevBuf ws;       /* device, in bytes: [row flags n2 nb | column flags n1 nb | ok max(n1, n2) nb] of one chunk */
 };
 
-enum { PROD_ENCODE, PROD_DECODE, PROD_CHECK };
-
 struct ProdCall {
-    int op;
+    FormOp op;
     uint8_t *blocks;
     size_t pitch, bstride, k1, k2, count;
     int first_axis;
@@ -3909,10 +3884,10 @@ EXPORT void poporon_amd_product_destroy(poporon_product_t *p)
 {
     if (!p)
         return;
-    if (p->ws && p->h[0] && p->h[0]->gpu.ready) {
+    if (p->ws.p && p->h[0] && p->h[0]->gpu.ready) {
         DeviceGuard dg(p->h[0]->gpu.device);
         (void)hipDeviceSynchronize();
-        (void)hipFree(p->ws);
+        (void)hipFree(p->ws.p);
     }
     poporon_destroy(p->h[0]);
     poporon_destroy(p->h[1]);
@@ -3941,8 +3916,6 @@ EXPORT poporon_product_t *poporon_amd_product_create(const poporon_config_t *row
     poporon_product_t *p = new (std::nothrow) _poporon_product_t();
     if (!p)
         return nullptr;
-    p->ws = nullptr;
-    p->ws_bytes = 0;
     p->h[0] = poporon_create(row_config);
     p->h[1] = poporon_create(col_config);
     for (int a = 0; a < 2; a++) {
@@ -4004,13 +3977,13 @@ static bool prod_args(const poporon_product_t *p, const char *what, const ProdCa
     if (c.pitch > ((size_t)-1 - n1) / n2 || c.bstride < (n2 - 1) * c.pitch + n1)
         return fail("%s: block_stride %zu < (n2 - 1) * row_pitch + n1 = %zu", what, c.bstride,
                     (n2 - 1) * c.pitch + n1);
-    if (c.op == PROD_DECODE) {
+    if (c.op == FORM_DECODE) {
         if (c.first_axis != 0 && c.first_axis != 1)
             return fail("%s: first_axis %d is neither 0 nor 1", what, c.first_axis);
         if (c.passes < 1 || c.passes > 16)
             return fail("%s: passes %zu outside [1, 16]", what, c.passes);
     }
-    if (c.op != PROD_ENCODE && !c.row_dirty && !c.col_dirty && !c.block_ok)
+    if (c.op != FORM_ENCODE && !c.row_dirty && !c.col_dirty && !c.block_ok)
         return fail("%s: NULL argument (d_row_dirty, d_col_dirty and d_block_ok)", what);
     if (c.count == 0)
         return true;
@@ -4047,29 +4020,26 @@ static bool prod_enter(poporon_product_t *p)
 static bool prod_ensure_ws(poporon_product_t *p, size_t n1, size_t n2, size_t nb)
 {
     const size_t need = nb * (n1 + n2 + std::max(n1, n2));
-    if (p->ws_bytes >= need)
+    if (p->ws.cap >= need)
         return true;
-    if (p->ws) {
-        for (int a = 0; a < 2; a++) {
-            GpuCtx &g = p->h[a]->gpu;
-            if (g.rem_pending)
-                HIP_OK(hipEventSynchronize(g.rem_done));
-            g.rem_pending = false;
-        }
-        HIP_OK(hipFree(p->ws));
-        p->ws = nullptr;
-        p->ws_bytes = 0;
+    for (int a = 0; p->ws.p && a < 2; a++) {
+        GpuCtx &g = p->h[a]->gpu;
+        if (g.rem_pending)
+            HIP_OK(hipEventSynchronize(g.rem_done));
+        g.rem_pending = false;
     }
-    HIP_OK(hipMalloc((void **)&p->ws, need));
-    p->ws_bytes = need;
-    return true;
+    return buf_renew(p->ws, need, 1);
 }
 
 static bool prod_reserve(poporon_product_t *p, size_t n1, size_t n2, size_t nb)
 {
-    return prod_ensure_ws(p, n1, n2, nb) && ensure_ilv(p->h[0], nb * n2) && ensure_ilv(p->h[1], nb * n1) &&
-           ensure_rem(p->h[0], nb * n2) && ensure_rem(p->h[1], nb * n1) && ensure_plist(p->h[0], nb * n2) &&
-           ensure_plist(p->h[1], nb * n1);
+    if (!prod_ensure_ws(p, n1, n2, nb))
+        return false;
+    const size_t cw[2] = {nb * n2, nb * n1}; /* codewords of axis a in a chunk */
+    for (int a = 0; a < 2; a++)
+        if (!ensure_ilv(p->h[a], cw[a]) || !ensure_rem(p->h[a], cw[a]) || !ensure_plist(p->h[a], cw[a]))
+            return false;
+    return true;
 }
 
 /* device pointers; the caller holds both batch scopes and the device */
@@ -4086,7 +4056,7 @@ static bool prod_run(poporon_product_t *p, const ProdCall &c, hipStream_t s)
         return false;
     if (!ensure_ilv(h1, nb0 * n[0]) || ((!inplace) && !ensure_ilv(h0, nb0 * n[1])))
         return false;
-    if (c.op == PROD_DECODE && c.couple) /* passes 1, 2, ... take lists: the second axis, then the first again */
+    if (c.op == FORM_DECODE && c.couple) /* passes 1, 2, ... take lists: the second axis, then the first again */
         for (size_t pass = 1; pass < std::min<size_t>(c.passes, 3); pass++) {
             const int a = (c.first_axis + (int)pass) & 1;
             if (!ensure_plist(p->h[a], nb0 * cwn[a]))
@@ -4097,9 +4067,9 @@ static bool prod_run(poporon_product_t *p, const ProdCall &c, hipStream_t s)
     for (size_t b0 = 0; b0 < c.count; b0 += chunk) {
         const size_t nb = std::min(chunk, c.count - b0);
         uint8_t *blk = c.blocks + b0 * c.bstride;
-        uint8_t *flag[2] = {c.row_dirty ? c.row_dirty + b0 * n[1] : p->ws,
-                            c.col_dirty ? c.col_dirty + b0 * n[0] : p->ws + nb0 * n[1]};
-        uint8_t *okbuf = p->ws + nb0 * (n[0] + n[1]);
+        uint8_t *flag[2] = {c.row_dirty ? c.row_dirty + b0 * n[1] : p->ws.p,
+                            c.col_dirty ? c.col_dirty + b0 * n[0] : p->ws.p + nb0 * n[1]};
+        uint8_t *okbuf = p->ws.p + nb0 * (n[0] + n[1]);
         /* axis a's codewords of the chunk as rows: where they are, gathered first unless they are the block rows */
         auto stage = [&](int a, uint32_t cw, uint32_t m1, uint8_t *&data, size_t &ds) -> bool {
             poporon_t *h = p->h[a];
@@ -4108,7 +4078,7 @@ static bool prod_run(poporon_product_t *p, const ProdCall &c, hipStream_t s)
                 ds = c.pitch;
                 return true;
             }
-            data = h->gpu.ilv;
+            data = h->gpu.ilv.p;
             ds = n[a];
             STAGE(h->gpu, POPORON_AMD_KERNEL_PROD_GATHER, s,
                   rsk_prod_gather(blk, c.pitch, c.bstride, nb, (uint32_t)a, n[a], cw, 0u, m1, data, s));
@@ -4119,7 +4089,7 @@ static bool prod_run(poporon_product_t *p, const ProdCall &c, hipStream_t s)
             if (a == 0 && inplace)
                 return true;
             STAGE(h->gpu, POPORON_AMD_KERNEL_PROD_SCATTER, s,
-                  rsk_prod_scatter(h->gpu.ilv, blk, c.pitch, c.bstride, nb, (uint32_t)a, n[a], cw, m0, n[a], s));
+                  rsk_prod_scatter(h->gpu.ilv.p, blk, c.pitch, c.bstride, nb, (uint32_t)a, n[a], cw, m0, n[a], s));
             return true;
         };
         auto check = [&](int a) -> bool {
@@ -4128,7 +4098,7 @@ static bool prod_run(poporon_product_t *p, const ProdCall &c, hipStream_t s)
             return stage(a, cwn[a], n[a], data, ds) &&
                    launch_check(p->h[a], data, ds, data + k[a], ds, k[a], nb * cwn[a], flag[a], s);
         };
-        if (c.op == PROD_ENCODE) {
+        if (c.op == FORM_ENCODE) {
             /* column parity of the message columns, then row parity of every row: the checks on checks come out
              * the same either way round (one field) */
             for (int a = 1; a >= 0; a--) {
@@ -4141,7 +4111,7 @@ static bool prod_run(poporon_product_t *p, const ProdCall &c, hipStream_t s)
             }
             continue;
         }
-        if (c.op == PROD_CHECK) {
+        if (c.op == FORM_CHECK) {
             if (!check(0) || !check(1))
                 return false;
         } else {
@@ -4153,15 +4123,15 @@ static bool prod_run(poporon_product_t *p, const ProdCall &c, hipStream_t s)
                 const bool lists = c.couple && pass > 0;
                 if (lists)
                     STAGE(g, POPORON_AMD_KERNEL_PROD_LISTS, s,
-                          rsk_prod_lists(flag[a ^ 1], n[a], r[a], cwn[a], g.plist, (uint32_t)ls,
-                                         g.plist + g.plist_cap * ls, nb, s));
+                          rsk_prod_lists(flag[a ^ 1], n[a], r[a], cwn[a], g.plist.p, (uint32_t)ls,
+                                         g.plist.p + g.plist.cap * ls, nb, s));
                 uint8_t *data;
                 size_t ds;
                 if (!stage(a, cwn[a], n[a], data, ds))
                     return false;
                 const DecodeCall d = {.data = data, .ds = ds, .par = data + k[a], .ps = ds, .size = k[a], .count = ncw,
-                                      .pos8 = lists ? g.plist : nullptr, .pos_stride = ls,
-                                      .cnt = lists ? g.plist + g.plist_cap * ls : nullptr, .ok = okbuf,
+                                      .pos8 = lists ? g.plist.p : nullptr, .pos_stride = ls,
+                                      .cnt = lists ? g.plist.p + g.plist.cap * ls : nullptr, .ok = okbuf,
                                       .corrected = nullptr, .s = s};
                 if (!launch_decode(h, d) || !launch_check(h, data, ds, data + k[a], ds, k[a], ncw, flag[a], s) ||
                     !unstage(a, cwn[a], 0u))
@@ -4177,17 +4147,22 @@ static bool prod_run(poporon_product_t *p, const ProdCall &c, hipStream_t s)
     return rem_release(h0->gpu, s) && rem_release(h1->gpu, s);
 }
 
-static bool prod_device(poporon_product_t *p, const char *what, const ProdCall &c, void *stream)
+/* form_scope over both handles */
+template <class F> static bool prod_scope(poporon_product_t *p, size_t count, void *stream, bool host, F &&run)
 {
-    if (!prod_args(p, what, c))
-        return false;
-    if (c.count == 0)
+    if (count == 0)
         return true;
     if (!prod_enter(p))
         return false;
-    BatchScope bs0{p->h[0]->gpu, (hipStream_t)stream, false}, bs1{p->h[1]->gpu, (hipStream_t)stream, false};
+    BatchScope bs0{p->h[0]->gpu, (hipStream_t)stream, host}, bs1{p->h[1]->gpu, (hipStream_t)stream, host};
     DeviceGuard dg(p->h[0]->gpu.device);
-    return prod_run(p, c, (hipStream_t)stream);
+    return run((hipStream_t)stream);
+}
+
+static bool prod_device(poporon_product_t *p, const char *what, const ProdCall &c, void *stream)
+{
+    return prod_args(p, what, c) &&
+           prod_scope(p, c.count, stream, false, [&](hipStream_t s) { return prod_run(p, c, s); });
 }
 
 EXPORT bool poporon_amd_product_reserve(poporon_product_t *p, size_t row_size, size_t col_size, size_t max_blocks)
@@ -4208,7 +4183,7 @@ EXPORT bool poporon_encode_product_device(poporon_product_t *p, uint8_t *d_block
                                           size_t block_stride, size_t row_size, size_t col_size, size_t count,
                                           void *stream)
 {
-    const ProdCall c = {PROD_ENCODE, d_blocks, row_pitch, block_stride, row_size, col_size, count, 0, 0, 0,
+    const ProdCall c = {FORM_ENCODE, d_blocks, row_pitch, block_stride, row_size, col_size, count, 0, 0, 0,
                         nullptr,     nullptr,  nullptr};
     return prod_device(p, "poporon_encode_product_device", c, stream);
 }
@@ -4218,7 +4193,7 @@ EXPORT bool poporon_decode_product_device(poporon_product_t *p, uint8_t *d_block
                                           int first_axis, size_t passes, int couple, uint8_t *d_row_dirty,
                                           uint8_t *d_col_dirty, uint8_t *d_block_ok, void *stream)
 {
-    const ProdCall c = {PROD_DECODE, d_blocks, row_pitch, block_stride, row_size,    col_size,   count,
+    const ProdCall c = {FORM_DECODE, d_blocks, row_pitch, block_stride, row_size,    col_size,   count,
                         first_axis,  passes,   couple,    d_row_dirty,  d_col_dirty, d_block_ok};
     return prod_device(p, "poporon_decode_product_device", c, stream);
 }
@@ -4227,7 +4202,7 @@ EXPORT bool poporon_check_product_device(poporon_product_t *p, const uint8_t *d_
                                          size_t block_stride, size_t row_size, size_t col_size, size_t count,
                                          uint8_t *d_row_dirty, uint8_t *d_col_dirty, uint8_t *d_block_ok, void *stream)
 {
-    const ProdCall c = {PROD_CHECK, const_cast<uint8_t *>(d_blocks), row_pitch, block_stride, row_size, col_size,
+    const ProdCall c = {FORM_CHECK, const_cast<uint8_t *>(d_blocks), row_pitch, block_stride, row_size, col_size,
                         count,      0, 0, 0, d_row_dirty, d_col_dirty, d_block_ok};
     return prod_device(p, "poporon_check_product_device", c, stream);
 }
@@ -4237,19 +4212,11 @@ EXPORT bool poporon_check_product_device(poporon_product_t *p, const uint8_t *d_
  * [blocks n1 n2 n | row flags n2 n | column flags n1 n | block ok n] */
 static const size_t kProdHostBytes = (size_t)8 << 20;
 
-static bool prod_host(poporon_product_t *p, const char *what, const ProdCall &c)
+static bool prod_host_run(poporon_product_t *p, const ProdCall &c)
 {
-    if (!prod_args(p, what, c))
-        return false;
-    if (c.count == 0)
-        return true;
-    if (!prod_enter(p))
-        return false;
-    BatchScope bs0{p->h[0]->gpu, nullptr, true}, bs1{p->h[1]->gpu, nullptr, true};
-    DeviceGuard dg(p->h[0]->gpu.device);
     const size_t n1 = c.k1 + p->h[0]->rs->num_roots, n2 = c.k2 + p->h[1]->rs->num_roots, bb = n1 * n2;
     const size_t chunk = std::max<size_t>(1, std::min(c.count, kProdHostBytes / (bb + n1 + n2 + 1)));
-    const bool enc = c.op == PROD_ENCODE;
+    const bool enc = c.op == FORM_ENCODE;
     auto o_row = [&](size_t n) { return n * bb; };
     auto o_col = [&](size_t n) { return o_row(n) + n * n2; };
     auto o_ok = [&](size_t n) { return o_col(n) + n * n1; };
@@ -4296,10 +4263,16 @@ static bool prod_host(poporon_product_t *p, const char *what, const ProdCall &c)
         "HIP failure in a product-code host batch");
 }
 
+static bool prod_host(poporon_product_t *p, const char *what, const ProdCall &c)
+{
+    return prod_args(p, what, c) &&
+           prod_scope(p, c.count, nullptr, true, [&](hipStream_t) { return prod_host_run(p, c); });
+}
+
 EXPORT bool poporon_encode_product(poporon_product_t *p, uint8_t *blocks, size_t row_pitch, size_t block_stride,
                                    size_t row_size, size_t col_size, size_t count)
 {
-    const ProdCall c = {PROD_ENCODE, blocks, row_pitch, block_stride, row_size, col_size, count, 0, 0, 0,
+    const ProdCall c = {FORM_ENCODE, blocks, row_pitch, block_stride, row_size, col_size, count, 0, 0, 0,
                         nullptr,     nullptr, nullptr};
     return prod_host(p, "poporon_encode_product", c);
 }
@@ -4308,7 +4281,7 @@ EXPORT bool poporon_decode_product(poporon_product_t *p, uint8_t *blocks, size_t
                                    size_t row_size, size_t col_size, size_t count, int first_axis, size_t passes,
                                    int couple, uint8_t *row_dirty, uint8_t *col_dirty, uint8_t *block_ok)
 {
-    const ProdCall c = {PROD_DECODE, blocks, row_pitch, block_stride, row_size,  col_size, count,
+    const ProdCall c = {FORM_DECODE, blocks, row_pitch, block_stride, row_size,  col_size, count,
                         first_axis,  passes, couple,    row_dirty,    col_dirty, block_ok};
     return prod_host(p, "poporon_decode_product", c);
 }
