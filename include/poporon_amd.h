@@ -631,6 +631,74 @@ bool poporon_decode_product(poporon_product_t *prod, uint8_t *blocks, size_t row
                             size_t row_size, size_t col_size, size_t count, int first_axis, size_t passes, int couple,
                             uint8_t *row_dirty, uint8_t *col_dirty, uint8_t *block_ok);
 
+/* ---- soft-decision RS decode: Chase-2 over bit LLRs ---------------------------
+ * The row decode takes hard symbols.  A demodulator knows more: how reliable
+ * every bit was.  This call takes that, as int8 LLRs, and spends the errors-only
+ * row decode 2^flips times per codeword on it: the `flips` least reliable bits
+ * are tried both ways, every trial row is decoded, and the decoded codeword
+ * closest to the LLRs wins.  Every step is integer arithmetic and pinned here,
+ * so the result is defined bit for bit (tests/soft_ref.py is the model).
+ *
+ * Let m = symbol_size (2..8), nr = num_roots, W = size + nr.
+ *
+ * Input.  Codeword c has W*m int8 values at d_llr + c*llr_stride: the value of
+ * bit j of symbol s, MSB first (j = 0 is the symbol's bit m-1), at index
+ * s*m + j; message symbols 0 .. size-1 first, then the parity symbols.
+ * Negative means 1, >= 0 means 0 (the LDPC soft path's convention).  The
+ * contents of the rows at d_data / d_parity are NOT an input.
+ *  1. Hard row.  hard[s] = sum over j of (llr[s*m + j] < 0) << (m-1-j).
+ *  2. Pick.  A bit's magnitude is |llr| as an int (-128 gives 128).  The picked
+ *     bits q_0 .. q_(flips-1) are the first `flips` bit indices in ascending
+ *     order of (magnitude, bit index): ties go to the lower index.
+ *  3. Candidates.  For p = 0 .. 2^flips - 1, candidate p is the hard row with bit
+ *     q_k flipped wherever bit k of p is set.
+ *  4. Decode.  Every candidate goes through the errors-only row decode, routed
+ *     by the number of candidate rows of the chunk as any batch of that many
+ *     rows is; its result is poporon_decode_batch_device's for that row (the
+ *     reference's, quirks Q6/Q8 included).  A candidate whose decode fails is
+ *     ignored, whatever the failed decode left in its row.
+ *  5. Score and select.  The score of a candidate that decoded to row y is the
+ *     sum of the magnitudes of all bits in which y differs from the hard row (at
+ *     most 2040 * 128).  The winner is the smallest score, ties to the lowest p.
+ *  6. Output.  With a winner: d_data / d_parity of codeword c get y, d_ok[c] = 1,
+ *     d_changed[c] = the number of symbols with y != hard, d_pattern[c] = p,
+ *     d_score[c] = the winner's score.  Without one: the rows get the hard row,
+ *     d_ok[c] = 0 and the other three are 0.
+ * flips = 0 is therefore poporon_decode_batch_device on the hard rows: the same
+ * ok, and the same bytes wherever ok = 1 (a failed row comes back as the hard
+ * row here).
+ *
+ * d_changed, d_pattern and d_score (4-byte aligned) may be NULL; d_ok may not.
+ * Data and parity may lie anywhere, at any alignment and stride, as for
+ * poporon_decode_batch_device; bytes between rows are never written, and d_llr
+ * (any alignment) is never written.  count 0 returns true without a GPU.  The
+ * call fails before it touches the GPU, with a message, for a NULL or non-RS
+ * handle, size outside [1, kmax], flips > 6 or flips > W*m, llr_stride < W*m,
+ * data_stride < size, parity_stride < nr, and NULL d_llr, d_data, d_parity or
+ * d_ok.  There are no erasure lists and no external syndromes on this call, and
+ * they do not combine with it: an erasure-mode decode that also meets plain
+ * errors pairs magnitudes with the wrong slots and returns ok with wrong bytes
+ * (quirk Q2), so candidates could not be trusted.  A wire form set on the
+ * handle is NOT applied.  There is no host form.  Asynchronous on `stream`.
+ *
+ * How: chunks of max(1, POPORON_AMD_ILV_CHUNK >> flips) codewords (default 2^20
+ * candidate rows) run one after another on `stream`.  rs_soft_expand_k writes a
+ * chunk's candidates into the staging rows of the interleaved calls (256 bytes
+ * each, candidate p of the chunk's codeword i at row (i << flips) + p), the row
+ * decode runs there with its ok / corrected in a buffer the handle owns, and
+ * rs_soft_select_k scores the candidates and writes the caller's arrays
+ * (rs_soft.hip).  poporon_amd_reserve_soft sizes the staging rows, that buffer
+ * and the decoders' workspace for min(max_codewords, chunk) << flips rows, after
+ * which soft calls with that `flips` allocate nothing. */
+/* (size + num_roots) * symbol_size: the int8 values of one codeword; 0 for a handle that is no RS handle or a size
+ * outside [1, kmax].  No GPU. */
+size_t poporon_amd_soft_llr_row(const poporon_t *pprn, size_t size);
+bool poporon_amd_reserve_soft(poporon_t *pprn, unsigned flips, size_t max_codewords);
+bool poporon_decode_soft_batch_device(poporon_t *pprn, const int8_t *d_llr, size_t llr_stride, uint8_t *d_data,
+                                      size_t data_stride, uint8_t *d_parity, size_t parity_stride, size_t size,
+                                      size_t count, unsigned flips, uint8_t *d_ok, uint8_t *d_changed,
+                                      uint8_t *d_pattern, uint32_t *d_score, void *stream);
+
 /* ---- LDPC batches -----------------------------------------------------------
  * Row c has info_bytes (poporon_get_info_size) of data at d_data +
  * c*data_stride and parity_bytes (poporon_get_parity_size) of parity at
@@ -741,6 +809,10 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
  * pass and chunk on the pass's handle, and rs_prod_ok_k, one per chunk on the
  * row handle when d_block_ok is given.  The codec kernels keep their ids; a
  * pass's flags are one more launch of 3.
+ * The soft call: 27 = LLR rows to candidate rows (rs_soft_expand_k), 28 = the
+ * candidates' scores and the winner's row (rs_soft_select_k), one launch each
+ * per chunk; the decode of the candidates between them keeps its ids, routed by
+ * the chunk's count of candidate rows.
  *
  * Error- and erasure-mode batches of at least 16384 codewords take the split
  * decode; POPORON_AMD_DECODE_PATH=split / single / wave in the environment
@@ -771,6 +843,7 @@ bool poporon_amd_ldpc_graph(const poporon_t *pprn, uint32_t *num_checks, uint32_
 /* the plane calls' ids are enumerators: tests/test_conv_cpu.py pins the macro ids above to 22 of them */
 enum { POPORON_AMD_KERNEL_PLANE_GATHER = 22, POPORON_AMD_KERNEL_PLANE_SCATTER = 23 };
 enum { POPORON_AMD_KERNEL_PROD_GATHER = 24, POPORON_AMD_KERNEL_PROD_SCATTER = 25, POPORON_AMD_KERNEL_PROD_LISTS = 26 };
+enum { POPORON_AMD_KERNEL_SOFT_EXPAND = 27, POPORON_AMD_KERNEL_SOFT_SELECT = 28 };
 bool poporon_amd_timing(poporon_t *pprn, int enable);
 bool poporon_amd_timing_read(poporon_t *pprn, int kernel, double *total_ms, uint64_t *launches);
 

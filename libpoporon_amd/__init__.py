@@ -141,6 +141,10 @@ _SIGS = {
                                                         C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     "poporon_check_planes_strided_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t,
                                                        C.c_size_t, _vp, _vp]),
+    "poporon_amd_soft_llr_row": (C.c_size_t, [_vp, C.c_size_t]),
+    "poporon_amd_reserve_soft": (C.c_bool, [_vp, C.c_uint, C.c_size_t]),
+    "poporon_decode_soft_batch_device": (C.c_bool, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t,
+                                                    C.c_size_t, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
     "poporon_amd_product_create": (_vp, [_vp, _vp]),
     "poporon_amd_product_destroy": (None, [_vp]),
     "poporon_amd_product_handle": (_vp, [_vp, C.c_int]),
@@ -215,6 +219,9 @@ KERNEL_PROD_GATHER, KERNEL_PROD_SCATTER, KERNEL_PROD_LISTS = 24, 25, 26
 PROD_KERNEL_NAMES = {KERNEL_PROD_GATHER: "rs_prod_gather_k (block to rows)",
                      KERNEL_PROD_SCATTER: "rs_prod_scatter_k (rows to block)",
                      KERNEL_PROD_LISTS: "rs_prod_lists_k / rs_prod_ok_k"}
+KERNEL_SOFT_EXPAND, KERNEL_SOFT_SELECT = 27, 28
+SOFT_KERNEL_NAMES = {KERNEL_SOFT_EXPAND: "rs_soft_expand_k (LLR rows to candidate rows)",
+                     KERNEL_SOFT_SELECT: "rs_soft_select_k (scores and the winner's row)"}
 LDPC_KERNEL_NAMES = {KERNEL_LDPC_ENCODE: "ldpc_encode_k", KERNEL_LDPC_DECODE: "ldpc_decode_k",
                      KERNEL_LDPC_CHECK: "ldpc_check_k"}
 
@@ -776,6 +783,23 @@ class Poporon:
                                                                  parity_plane_stride, size, count, d_dirty,
                                                                  stream or None),
                     "poporon_check_planes_strided_device")
+
+    # ---- soft-decision decode: Chase-2 over int8 bit LLRs (include/poporon_amd.h) ------
+    # codeword c: soft_llr_row(size) int8 values at llr_ptr + c*llr_stride, bit j (MSB first) of symbol s
+    # at s*symbol_size + j, negative = 1; the rows at data_ptr / par_ptr are outputs only
+    def soft_llr_row(self, size):
+        return int(self.lib.poporon_amd_soft_llr_row(self.h, size))
+
+    def reserve_soft(self, flips, max_codewords):
+        self._check(self.lib.poporon_amd_reserve_soft(self.h, flips, max_codewords), "poporon_amd_reserve_soft")
+
+    def decode_soft_batch_device(self, llr_ptr, llr_stride, data_ptr, ds, par_ptr, ps, size, count, flips, ok_ptr,
+                                 changed_ptr=0, pattern_ptr=0, score_ptr=0, stream=0):
+        self._check(self.lib.poporon_decode_soft_batch_device(self.h, llr_ptr or None, llr_stride, data_ptr or None, ds,
+                                                              par_ptr or None, ps, size, count, flips, ok_ptr or None,
+                                                              changed_ptr or None, pattern_ptr or None,
+                                                              score_ptr or None, stream or None),
+                    "poporon_decode_soft_batch_device")
 
     # ---- in-library kernel timing (HIP events on the launch stream) ---------------
     def timing(self, enable: bool):

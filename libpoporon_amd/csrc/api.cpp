@@ -118,7 +118,7 @@ struct _poporon_config_t {
     uint64_t seed;
 };
 
-#define NKERN 27
+#define NKERN 29
 struct TimedLaunch {
     int kernel;
     hipEvent_t a, b;
@@ -156,6 +156,9 @@ struct GpuCtx {
     /* the plane calls' erasure lists (rs_planes.hip): plist.cap rows of plane_list_stride bytes, then plist.cap
      * counts; ordered as ilv is */
     DevBuf plist;
+    /* the soft call's candidates (rs_soft.hip): soft.cap ok flags of the staged candidate rows, then soft.cap
+     * corrected counts; ordered as ilv is */
+    DevBuf soft;
     /* the wire form's device image (RS_ILV_WIRE_BYTES, rs_device.h); wire_ok: it
      * holds the handle's form as last set (ensure_wire) */
     uint8_t *wire = nullptr;
@@ -1125,7 +1128,7 @@ static void gpu_release(GpuCtx &g)
 {
     const int dev = g.device;
     const bool any = g.ready || g.stream || g.sstream || g.tab || g.gtab || g.rem || g.ltab || g.lws || g.stage ||
-                     g.hstage || g.zc || g.ilv.p || g.rep.p || g.plist.p || g.wire || g.rslot.stream ||
+                     g.hstage || g.zc || g.ilv.p || g.rep.p || g.plist.p || g.soft.p || g.wire || g.rslot.stream ||
                      g.rem_done || g.registered || g.batch_ev ||
                      g.pipe[0].stream || g.pipe[1].stream || g.pipe[2].stream;
     if (!any || dev < 0) {
@@ -1154,7 +1157,7 @@ static void gpu_release(GpuCtx &g)
     (void)hipFree(g.tab);
     (void)hipFree(g.gtab);
     (void)hipFree(g.rem);
-    for (DevBuf *b : {&g.ilv, &g.rep, &g.plist})
+    for (DevBuf *b : {&g.ilv, &g.rep, &g.plist, &g.soft})
         (void)hipFree(b->p);
     (void)hipFree(g.wire);
     (void)hipFree(g.ltab);
@@ -1404,7 +1407,7 @@ static bool buf_renew(DevBuf &b, size_t cap, size_t unit_bytes)
 }
 
 /* The handle's buffers that the layout forms share across streams under rem's
- * ordering (ilv, rep, plist): at least `units` units of unit_bytes, min_units
+ * ordering (ilv, rep, plist, soft): at least `units` units of unit_bytes, min_units
  * when it is allocated at all.  The last reader of the old buffer may run on
  * any stream the caller chose: wait for it before the free. */
 static bool ensure_buf(GpuCtx &g, DevBuf &b, size_t units, size_t unit_bytes, size_t min_units)
@@ -3741,6 +3744,121 @@ EXPORT bool poporon_check_planes_strided_device(poporon_t *h, const uint8_t *d_d
     const PlaneCall c = {FORM_CHECK, nullptr, size, count, nullptr, 0, nullptr, nullptr, d_dirty, {}};
     return plane_strided(h, "poporon_check_planes_strided_device", c, d_data, data_plane_stride, d_parity,
                          parity_plane_stride, stream);
+}
+
+/* ------------------------------------------------------------------------ */
+/* soft-decision decode: Chase-2 around the errors-only row decode          */
+/* ------------------------------------------------------------------------ */
+
+/*
+ * A chunk of n codewords is n << flips candidate rows in the staging rows
+ * (rs_soft.hip; RS_ILV_ROW bytes from one to the next, so that every row starts
+ * on a 16-byte boundary and both kernels move whole uint4 slots; rows packed
+ * back to back were measured and not kept), one launch_decode
+ * over all of them, routed by that count, with its ok / corrected per candidate
+ * in the handle's soft buffer, and the selection into the caller's arrays.  The
+ * loop is its own, beside form_chunks: the
+ * decode's result arrays are per candidate, not per caller codeword, and
+ * nothing is gathered from or scattered to the caller's rows.  The ordering of
+ * the shared buffers across streams is the staged forms'.
+ */
+#define SOFT_MAX_FLIPS 6u
+
+struct SoftCall {
+    const int8_t *llr;
+    size_t ls;
+    uint8_t *data;
+    size_t ds;
+    uint8_t *par;
+    size_t ps;
+    size_t size, count;
+    unsigned flips;
+    uint8_t *ok, *changed, *pattern;
+    uint32_t *score;
+};
+
+static size_t soft_chunk(const poporon_t *h, unsigned flips) { return std::max<size_t>(1, h->ilv_chunk >> flips); }
+
+static bool ensure_soft(poporon_t *h, size_t rows) { return ensure_buf(h->gpu, h->gpu.soft, rows, 2, 0); }
+
+static bool soft_flips(const poporon_t *h, const char *what, size_t size, unsigned flips)
+{
+    const size_t bits = (size + h->rs->num_roots) * h->rs->gf->symbol_size;
+    if (flips > SOFT_MAX_FLIPS)
+        return fail("%s: flips %u > %u", what, flips, SOFT_MAX_FLIPS);
+    if (flips > bits)
+        return fail("%s: flips %u > the %zu bits of a codeword", what, flips, bits);
+    return true;
+}
+
+/* the checks the soft call makes before it touches the GPU */
+static bool soft_args(const poporon_t *h, const char *what, const SoftCall &c)
+{
+    if (!rs_handle(h, what) || !form_size(h, what, c.size) || !soft_flips(h, what, c.size, c.flips))
+        return false;
+    const size_t nr = h->rs->num_roots, bits = (c.size + nr) * h->rs->gf->symbol_size;
+    if (c.ls < bits)
+        return fail("%s: llr_stride %zu < (size + num_roots) * symbol_size = %zu", what, c.ls, bits);
+    if (c.ds < c.size)
+        return fail("%s: data_stride %zu < size %zu", what, c.ds, c.size);
+    if (c.ps < nr)
+        return fail("%s: parity_stride %zu < num_roots %zu", what, c.ps, nr);
+    if (c.count && (!c.llr || !c.data || !c.par || !c.ok))
+        return fail("%s: NULL argument", what);
+    return true;
+}
+
+/* device pointers; the caller holds the batch scope and the device */
+static bool soft_run(poporon_t *h, const SoftCall &c, hipStream_t s)
+{
+    GpuCtx &g = h->gpu;
+    const uint32_t nr = h->rs->num_roots, size = (uint32_t)c.size, m = h->rs->gf->symbol_size;
+    const size_t chunk = soft_chunk(h, c.flips), r0 = std::min(c.count, chunk) << c.flips;
+    if (!ensure_ilv(h, r0) || !ensure_soft(h, r0) || !rem_acquire(g, s))
+        return false;
+    for (size_t c0 = 0; c0 < c.count; c0 += chunk) {
+        const size_t n = std::min(chunk, c.count - c0);
+        const int8_t *llr = c.llr + c0 * c.ls;
+        STAGE(g, POPORON_AMD_KERNEL_SOFT_EXPAND, s, rsk_soft_expand(llr, c.ls, g.ilv.p, size, nr, m, c.flips, n, s));
+        const DecodeCall d = {.data = g.ilv.p, .ds = RS_ILV_ROW, .par = g.ilv.p + size, .ps = RS_ILV_ROW, .size = c.size,
+                              .count = n << c.flips, .ok = g.soft.p, .corrected = g.soft.p + g.soft.cap, .s = s};
+        if (!launch_decode(h, d))
+            return false;
+        STAGE(g, POPORON_AMD_KERNEL_SOFT_SELECT, s,
+              rsk_soft_select(llr, c.ls, g.ilv.p, g.soft.p, size, nr, m, c.flips, n, c.data + c0 * c.ds, c.ds,
+                              c.par + c0 * c.ps, c.ps, c.ok + c0, c.changed ? c.changed + c0 : nullptr,
+                              c.pattern ? c.pattern + c0 : nullptr, c.score ? c.score + c0 : nullptr, s));
+    }
+    return rem_release(g, s);
+}
+
+EXPORT size_t poporon_amd_soft_llr_row(const poporon_t *h, size_t size)
+{
+    if (!h || h->fec_type != PPLN_FEC_RS || !check_decode_size(h, size))
+        return 0;
+    return (size + h->rs->num_roots) * h->rs->gf->symbol_size;
+}
+
+EXPORT bool poporon_amd_reserve_soft(poporon_t *h, unsigned flips, size_t max_codewords)
+{
+    const char *what = "poporon_amd_reserve_soft";
+    if (!rs_handle(h, what) || !soft_flips(h, what, kmax(h), flips))
+        return false;
+    return reserve_scope(h, what, [&] {
+        const size_t rows = std::min(max_codewords, soft_chunk(h, flips)) << flips;
+        return ensure_ilv(h, rows) && ensure_soft(h, rows) && ensure_rem(h, rows);
+    });
+}
+
+EXPORT bool poporon_decode_soft_batch_device(poporon_t *h, const int8_t *d_llr, size_t llr_stride, uint8_t *d_data,
+                                             size_t data_stride, uint8_t *d_parity, size_t parity_stride, size_t size,
+                                             size_t count, unsigned flips, uint8_t *d_ok, uint8_t *d_changed,
+                                             uint8_t *d_pattern, uint32_t *d_score, void *stream)
+{
+    const SoftCall c = {d_llr, llr_stride, d_data, data_stride, d_parity,  parity_stride, size,
+                        count, flips,      d_ok,   d_changed,   d_pattern, d_score};
+    return soft_args(h, "poporon_decode_soft_batch_device", c) &&
+           form_scope(h, count, stream, false, [&](hipStream_t s) { return soft_run(h, c, s); });
 }
 
 /* Host form: chunks of rows through one pinned slot of its own and the device

@@ -548,6 +548,32 @@ hipError_t rsk_mask_lists(const uint8_t *mask, size_t mstride, uint32_t size, ui
                           size_t nframes, uint8_t *pos, size_t pstride, uint8_t *cnt, uint8_t *over,
                           hipStream_t stream);
 
+/*
+ * Soft-decision decode, Chase-2 (rs_soft.hip), around a row decode of the
+ * candidates.  llr: n rows of (size + nr)*m int8 values llr_stride apart at
+ * any alignment (bit j of symbol s, MSB first, at s*m + j; negative = 1).
+ * rows: the chunk's staging rows, 16-byte aligned, RS_ILV_ROW bytes each
+ * (message at 0, parity at size); candidate p of codeword i is row
+ * (i << flips) + p.
+ *   rsk_soft_expand  the hard row of every codeword with its `flips` least
+ *                    reliable bits (keys |llr| << 11 | bit index, ascending)
+ *                    flipped in all 2^flips combinations -> rows
+ *   rsk_soft_select  of the candidates with cand_ok != 0 the decoded row with
+ *                    the smallest sum of |llr| over the bits that differ from
+ *                    the hard row, ties to the lowest p -> the caller's rows,
+ *                    ok = 1, changed (symbols that differ from the hard row),
+ *                    pattern (p), score; no such candidate: the hard row,
+ *                    ok = 0, the others 0.  changed / pattern / score may be
+ *                    NULL.
+ * size + nr <= 255, m <= 8, flips <= 6 and <= (size + nr)*m.
+ */
+hipError_t rsk_soft_expand(const int8_t *llr, size_t llr_stride, uint8_t *rows, uint32_t size, uint32_t nr, uint32_t m,
+                           uint32_t flips, size_t n, hipStream_t s);
+hipError_t rsk_soft_select(const int8_t *llr, size_t llr_stride, const uint8_t *rows, const uint8_t *cand_ok,
+                           uint32_t size, uint32_t nr, uint32_t m, uint32_t flips, size_t n, uint8_t *data, size_t ds,
+                           uint8_t *parity, size_t ps, uint8_t *ok, uint8_t *changed, uint8_t *pattern, uint32_t *score,
+                           hipStream_t s);
+
 #ifdef __cplusplus
 }
 #endif
