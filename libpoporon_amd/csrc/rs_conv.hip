@@ -45,7 +45,7 @@
  * first and last slot are partial; any other placement is cut per region.
  *
  * The branch of a slot's first byte is one reciprocal multiplication
- * (conv_mod); from byte to byte branch and index are stepped: no division in
+ * (slot16_divmod); from byte to byte branch and index are stepped: no division in
  * the inner step.  Everything inside a workgroup's window is indexed in 32
  * bits relative to the window; the window's own offset is size_t.
  *
@@ -77,18 +77,6 @@ struct RsConvArgs {
     uint32_t wire;       /* rows are wire rows: one run per tile */
     float inv;           /* 1 / I */
 };
-
-/* x mod m for x < 2^24 (x is exact in float, the quotient estimate off by at most one) */
-static __device__ __forceinline__ uint32_t conv_mod(uint32_t x, uint32_t m, float inv)
-{
-    const uint32_t q = (uint32_t)((float)x * inv);
-    int32_t r = (int32_t)(x - q * m);
-    if (r < 0)
-        r += (int32_t)m;
-    else if (r >= (int32_t)m)
-        r -= (int32_t)m;
-    return (uint32_t)r;
-}
 
 /* the 16-byte slots of the row regions of codewords [c0, c0 + tc): slot idx of
  * `total` is the part [kb, ke) of the slot at p + o0, whose first byte inside
@@ -140,23 +128,10 @@ static __device__ __forceinline__ bool conv_rows_slot(const RsConvArgs &a, const
         len = a.nr;
         base = row * r.w + a.size;
     }
-    if (!ilv_slot(p, len, q, o0, kb, ke))
+    if (!slot16_part(p, len, q, o0, kb, ke))
         return false;
     nrel = base + (uint32_t)(o0 + (int32_t)kb);
     return true;
-}
-
-/* one slot's store: whole as a uint4, else its bytes [kb, ke) */
-static __device__ __forceinline__ void conv_store16(uint8_t *p, int32_t o0, uint32_t kb, uint32_t ke, const uint32_t w[4])
-{
-    if (kb == 0u && ke == 16u) {
-        *reinterpret_cast<uint4 *>(p + o0) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 16u; k++)
-            if (k >= kb && k < ke)
-                p[o0 + (int32_t)k] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
-    }
 }
 
 /* rows out of a window image: byte nrel of the tile at src[nrel + b*D], b = (ph0 + nrel) mod I.  src is the LDS image
@@ -172,7 +147,8 @@ static __device__ __forceinline__ void conv_rows_out(const RsConvArgs &a, const 
         uint32_t kb, ke, nrel;
         if (!conv_rows_slot(a, r, c0, idx, p, o0, kb, ke, nrel))
             continue;
-        uint32_t b = conv_mod(ph0 + nrel, a.nb, a.inv);
+        uint32_t turn, b;
+        slot16_divmod(ph0 + nrel, a.nb, a.inv, turn, b);
         uint32_t i = nrel + b * a.d;
         uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -186,7 +162,7 @@ static __device__ __forceinline__ void conv_rows_out(const RsConvArgs &a, const 
                 }
             }
         }
-        conv_store16(p, o0, kb, ke, w);
+        slot16_store(p, o0, kb, ke, w);
     }
 }
 
@@ -213,23 +189,14 @@ __global__ __launch_bounds__(RS_CONV_THREADS) void rs_conv_gather_k(RsConvArgs a
     const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(run) & 15u);
     const uint32_t nq = (head + len + 15u) / 16u;
     /* a partial slot goes to LDS whole: the bytes outside the window are copies of bytes inside it, and are not used */
-    for (uint32_t base = threadIdx.x; base < nq; base += RS_CONV_THREADS * RS_CONV_BATCH) {
-        uint4 v[RS_CONV_BATCH];
-        bool in[RS_CONV_BATCH];
-#pragma unroll
-        for (uint32_t u = 0; u < RS_CONV_BATCH; u++) {
-            const uint32_t q = base + u * RS_CONV_THREADS;
-            int32_t o0;
-            uint32_t kb, ke;
-            in[u] = q < nq && ilv_slot(run, len, q, o0, kb, ke);
-            if (in[u])
-                v[u] = ilv_load16(run, o0, kb, ke);
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < RS_CONV_BATCH; u++)
-            if (in[u])
-                conv_lds[base + u * RS_CONV_THREADS] = v[u];
-    }
+    slot16_batched<RS_CONV_THREADS, RS_CONV_BATCH>(
+        nq,
+        [&](uint32_t q, Slot16 &sl, uint4 &v) {
+            sl.tag = q;
+            if (slot16_part(run, len, q, sl.o0, sl.kb, sl.ke))
+                v = slot16_load(run, sl.o0, sl.kb, sl.ke);
+        },
+        [&](const Slot16 &sl, const uint4 &v) { conv_lds[sl.tag] = v; });
     __syncthreads();
     conv_rows_out(a, reinterpret_cast<const uint8_t *>(conv_lds) + head, c0, tc, ph0);
 }
@@ -259,9 +226,10 @@ __global__ __launch_bounds__(RS_CONV_THREADS) void rs_conv_scatter_direct_k(RsCo
         uint32_t kb, ke, nrel;
         if (!conv_rows_slot(a, r, c0, idx, p, o0, kb, ke, nrel))
             continue;
-        const uint4 v = ilv_load16(p, o0, kb, ke);
+        const uint4 v = slot16_load(p, o0, kb, ke);
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        uint32_t b = conv_mod(ph0 + nrel, a.nb, a.inv);
+        uint32_t turn, b;
+        slot16_divmod(ph0 + nrel, a.nb, a.inv, turn, b);
         uint32_t i = nrel + b * a.d;
 #pragma unroll
         for (uint32_t k = 0; k < 16u; k++) {
@@ -301,35 +269,21 @@ __global__ __launch_bounds__(RS_CONV_THREADS) void rs_conv_scatter_k(RsConvArgs 
     const ConvRows r = conv_rows(a, tc);
     const uint32_t lh = r.wire ? (uint32_t)(reinterpret_cast<uintptr_t>(a.data + nbase) & 15u) : 0u;
     uint8_t *lds = reinterpret_cast<uint8_t *>(conv_lds) + lh;
-    for (uint32_t base = threadIdx.x; base < r.total; base += RS_CONV_THREADS * RS_CONV_BATCH) {
-        uint4 v[RS_CONV_BATCH];
-        uint32_t kb[RS_CONV_BATCH], ke[RS_CONV_BATCH], nrel[RS_CONV_BATCH];
-#pragma unroll
-        for (uint32_t u = 0; u < RS_CONV_BATCH; u++) {
-            const uint32_t idx = base + u * RS_CONV_THREADS;
+    slot16_batched<RS_CONV_THREADS, RS_CONV_BATCH>(
+        r.total,
+        [&](uint32_t idx, Slot16 &sl, uint4 &v) {
             uint8_t *p;
-            int32_t o0;
-            kb[u] = ke[u] = 0u;
-            if (idx < r.total && conv_rows_slot(a, r, ca, idx, p, o0, kb[u], ke[u], nrel[u]))
-                v[u] = ilv_load16(p, o0, kb[u], ke[u]);
-            else
-                kb[u] = ke[u] = 0u;
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < RS_CONV_BATCH; u++) {
-            if (kb[u] >= ke[u])
-                continue;
-            if (kb[u] == 0u && ke[u] == 16u && ((lh + nrel[u]) & 15u) == 0u) {
-                *reinterpret_cast<uint4 *>(lds + nrel[u]) = v[u];
+            if (conv_rows_slot(a, r, ca, idx, p, sl.o0, sl.kb, sl.ke, sl.tag)) /* the tag: nrel */
+                v = slot16_load(p, sl.o0, sl.kb, sl.ke);
+        },
+        [&](const Slot16 &sl, const uint4 &v) {
+            if (sl.kb == 0u && sl.ke == 16u && ((lh + sl.tag) & 15u) == 0u) {
+                *reinterpret_cast<uint4 *>(lds + sl.tag) = v;
             } else {
-                const uint32_t x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-                for (uint32_t k = 0; k < 16u; k++)
-                    if (k >= kb[u] && k < ke[u])
-                        lds[nrel[u] + k - kb[u]] = (uint8_t)(x[k >> 2] >> (8u * (k & 3u)));
+                const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+                slot16_spread(lds + sl.tag - sl.kb, 1, x, sl.kb, sl.ke); /* byte kb is serial number nrel */
             }
-        }
-    }
+        });
     __syncthreads();
     /* the stream out: offset p holds serial number p - b*D, b = (phase + p) mod I; a hole where that is outside the
      * batch, and where it is a parity symbol without a parity region */
@@ -344,7 +298,8 @@ __global__ __launch_bounds__(RS_CONV_THREADS) void rs_conv_scatter_k(RsConvArgs 
             continue;
         const uint32_t kb = s0 < lo ? (uint32_t)(lo - s0) : 0u, ke = hi - s0 < 16 ? (uint32_t)(hi - s0) : 16u;
         const uint32_t prel = (uint32_t)(pa + s0 + (int64_t)kb - (int64_t)nbase); /* >= 0: nbase <= plo */
-        uint32_t b = conv_mod(ph0 + prel, a.nb, a.inv);
+        uint32_t turn, b;
+        slot16_divmod(ph0 + prel, a.nb, a.inv, turn, b);
         int32_t n = (int32_t)prel - (int32_t)(b * a.d);
         uint32_t x[4] = {0u, 0u, 0u, 0u}, ok = 0u;
         /* offsets [H, count*W) hold no hole: a whole slot there (all but the two ends of the span) is 16 bytes of
@@ -367,8 +322,11 @@ __global__ __launch_bounds__(RS_CONV_THREADS) void rs_conv_scatter_k(RsConvArgs 
         for (uint32_t k = 0; k < 16u; k++) {
             if (k >= kb && k < ke) {
                 bool in = n >= 0 && n < (int32_t)rows_len;
-                if (in && nopar)
-                    in = conv_mod((uint32_t)n, w, 1.0f / (float)w) < a.size;
+                if (in && nopar) {
+                    uint32_t row, sym;
+                    slot16_divmod((uint32_t)n, w, 1.0f / (float)w, row, sym);
+                    in = sym < a.size;
+                }
                 if (in) {
                     x[k >> 2] |= (uint32_t)lds[n] << (8u * (k & 3u));
                     ok |= 1u << k;

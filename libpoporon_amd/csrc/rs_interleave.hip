@@ -93,41 +93,29 @@ static __device__ void ilv_region_in(uint8_t *lds, uint32_t pitch, const uint8_t
 {
     const uint32_t len = nsym * depth;
     const uint32_t nq = len / 16u + 2u; /* slots a region can touch at the worst alignment */
-    for (uint32_t base = threadIdx.x; base < fc * nq; base += RS_ILV_THREADS * RS_ILV_BATCH) {
-        uint4 v[RS_ILV_BATCH];
-        uint32_t fi[RS_ILV_BATCH], kb[RS_ILV_BATCH], ke[RS_ILV_BATCH];
-        int32_t o0[RS_ILV_BATCH];
-#pragma unroll
-        for (uint32_t u = 0; u < RS_ILV_BATCH; u++) {
-            const uint32_t idx = base + u * RS_ILV_THREADS;
-            kb[u] = ke[u] = 0u; /* nothing of this slot */
-            if (idx < fc * nq) {
-                fi[u] = idx / nq;
-                const uint8_t *p = reg + (size_t)(f0 + fi[u]) * stride;
-                if (ilv_slot(p, len, idx - fi[u] * nq, o0[u], kb[u], ke[u])) {
-                    v[u] = ilv_load16(p, o0[u], kb[u], ke[u]);
-                    if constexpr (MAP) {
-                        if (wf.xlen) {
-                            const uint4 x = ilv_seq16(wf, o0[u]);
-                            v[u] = make_uint4(v[u].x ^ x.x, v[u].y ^ x.y, v[u].z ^ x.z, v[u].w ^ x.w);
-                        }
-                    }
-                } else {
-                    kb[u] = ke[u] = 0u;
+    slot16_batched<RS_ILV_THREADS, RS_ILV_BATCH>(
+        fc * nq,
+        [&](uint32_t idx, Slot16 &sl, uint4 &v) {
+            sl.tag = idx / nq; /* the frame within the tile */
+            const uint8_t *p = reg + (size_t)(f0 + sl.tag) * stride;
+            if (!slot16_part(p, len, idx - sl.tag * nq, sl.o0, sl.kb, sl.ke))
+                return;
+            v = slot16_load(p, sl.o0, sl.kb, sl.ke);
+            if constexpr (MAP) {
+                if (wf.xlen) {
+                    const uint4 x = ilv_seq16(wf, sl.o0);
+                    v = make_uint4(v.x ^ x.x, v.y ^ x.y, v.z ^ x.z, v.w ^ x.w);
                 }
             }
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < RS_ILV_BATCH; u++) {
-            if (kb[u] >= ke[u])
-                continue;
-            const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-            const uint32_t o = (uint32_t)(o0[u] + (int32_t)kb[u]);
+        },
+        [&](const Slot16 &sl, const uint4 &v) {
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            const uint32_t o = (uint32_t)(sl.o0 + (int32_t)sl.kb);
             uint32_t j = o / depth, i = o - j * depth;
-            const uint32_t r0 = fi[u] * depth;
+            const uint32_t r0 = sl.tag * depth;
 #pragma unroll
             for (uint32_t k = 0; k < 16u; k++) {
-                if (k >= kb[u] && k < ke[u]) {
+                if (k >= sl.kb && k < sl.ke) {
                     uint8_t b = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
                     if constexpr (MAP)
                         b = wf.lut[b];
@@ -138,8 +126,7 @@ static __device__ void ilv_region_in(uint8_t *lds, uint32_t pitch, const uint8_t
                     }
                 }
             }
-        }
-    }
+        });
 }
 
 /* LDS rows -> frames, the same walk */
@@ -154,7 +141,7 @@ static __device__ void ilv_region_out(const uint8_t *lds, uint32_t pitch, uint8_
         uint8_t *p = reg + (size_t)(f0 + fi) * stride;
         int32_t o0;
         uint32_t kb, ke;
-        if (!ilv_slot(p, len, q, o0, kb, ke))
+        if (!slot16_part(p, len, q, o0, kb, ke))
             continue;
         const uint32_t o = (uint32_t)(o0 + (int32_t)kb);
         uint32_t j = o / depth, i = o - j * depth;
@@ -173,14 +160,7 @@ static __device__ void ilv_region_out(const uint8_t *lds, uint32_t pitch, uint8_
                 }
             }
         }
-        if (kb == 0u && ke == 16u) {
-            *reinterpret_cast<uint4 *>(p + o0) = make_uint4(w[0], w[1], w[2], w[3]);
-        } else {
-#pragma unroll
-            for (uint32_t k = 0; k < 16u; k++)
-                if (k >= kb && k < ke)
-                    p[o0 + (int32_t)k] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
-        }
+        slot16_store(p, o0, kb, ke, w);
     }
 }
 
@@ -228,19 +208,7 @@ static __device__ __forceinline__ void ilv_gather_body(uint4 *lds128, const RsIl
     __syncthreads();
     /* rows out (without the parity region its columns carry whatever LDS held:
      * they are the rows' own bytes, which the encode then writes) */
-    const uint32_t nq = (head + len + 15u) / 16u;
-    for (uint32_t q = threadIdx.x; q < nq; q += RS_ILV_THREADS) {
-        int32_t o0;
-        uint32_t kb, ke;
-        if (!ilv_slot(run, len, q, o0, kb, ke))
-            continue;
-        if (kb == 0u && ke == 16u) {
-            *reinterpret_cast<uint4 *>(run + o0) = lds128[q];
-        } else {
-            for (uint32_t k = kb; k < ke; k++)
-                run[o0 + (int32_t)k] = lds[o0 + (int32_t)k];
-        }
-    }
+    slot16_image_out<RS_ILV_THREADS>(run, len, lds128);
 }
 
 __global__ __launch_bounds__(RS_ILV_THREADS) void rs_ilv_gather_k(RsIlvArgs a)
@@ -274,39 +242,25 @@ static __device__ __forceinline__ void ilv_scatter_body(uint4 *lds128, const RsI
     /* rows in, RS_ILV_BATCH loads in flight per lane; parity only: the slots
      * that hold message bytes alone are passed by */
     const uint32_t nq = (head + len + 15u) / 16u;
-    for (uint32_t base = threadIdx.x; base < nq; base += RS_ILV_THREADS * RS_ILV_BATCH) {
-        uint4 v[RS_ILV_BATCH];
-        uint32_t kb[RS_ILV_BATCH], ke[RS_ILV_BATCH];
-        int32_t o0[RS_ILV_BATCH];
-#pragma unroll
-        for (uint32_t u = 0; u < RS_ILV_BATCH; u++) {
-            const uint32_t q = base + u * RS_ILV_THREADS;
-            kb[u] = ke[u] = 0u;
-            if (q >= nq || !ilv_slot(run, len, q, o0[u], kb[u], ke[u])) {
-                kb[u] = ke[u] = 0u;
-                continue;
-            }
-            if (!a.both && (uint32_t)(o0[u] + (int32_t)kb[u]) % w + (ke[u] - kb[u]) <= a.size) {
-                kb[u] = ke[u] = 0u;
-                continue;
-            }
-            v[u] = ilv_load16(run, o0[u], kb[u], ke[u]);
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < RS_ILV_BATCH; u++) {
-            if (kb[u] >= ke[u])
-                continue;
-            if (kb[u] == 0u && ke[u] == 16u) {
-                lds128[base + u * RS_ILV_THREADS] = v[u];
+    slot16_batched<RS_ILV_THREADS, RS_ILV_BATCH>(
+        nq,
+        [&](uint32_t q, Slot16 &sl, uint4 &v) {
+            sl.tag = q;
+            if (!slot16_part(run, len, q, sl.o0, sl.kb, sl.ke))
+                return;
+            if (!a.both && (uint32_t)(sl.o0 + (int32_t)sl.kb) % w + (sl.ke - sl.kb) <= a.size)
+                sl.kb = sl.ke = 0u;
+            else
+                v = slot16_load(run, sl.o0, sl.kb, sl.ke);
+        },
+        [&](const Slot16 &sl, const uint4 &v) {
+            if (sl.kb == 0u && sl.ke == 16u) {
+                lds128[sl.tag] = v;
             } else {
-                const uint32_t x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-                for (uint32_t k = 0; k < 16u; k++)
-                    if (k >= kb[u] && k < ke[u])
-                        lds[o0[u] + (int32_t)k] = (uint8_t)(x[k >> 2] >> (8u * (k & 3u)));
+                const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+                slot16_spread(lds + sl.o0, 1, x, sl.kb, sl.ke);
             }
-        }
-    }
+        });
     __syncthreads();
     if (a.both)
         ilv_region_out<MAP>(lds, w, a.data, a.dstride, a.size, a.depth, 0u, f0, fc, wf);

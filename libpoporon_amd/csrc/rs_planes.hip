@@ -70,46 +70,12 @@ struct RsPlaneLost {
     uint32_t m[8];
 };
 
-/* item i -> plane j = i / s, slot q = i mod s; i < 2^24 is exact in float, the estimate off by at most one */
-static __device__ __forceinline__ void plane_item(uint32_t i, uint32_t s, float inv, uint32_t &j, uint32_t &q)
-{
-    j = (uint32_t)((float)i * inv);
-    int32_t r = (int32_t)(i - j * s);
-    if (r < 0) {
-        r += (int32_t)s;
-        j--;
-    } else if (r >= (int32_t)s) {
-        r -= (int32_t)s;
-        j++;
-    }
-    q = (uint32_t)r;
-}
-
 /* the part [kb, ke) of slot q of a plane run of len bytes at p that lies inside it (p NULL: a run on a boundary) */
 template <bool AL>
 static __device__ __forceinline__ bool plane_slot(const uint8_t *p, uint32_t len, uint32_t q, int32_t &o0, uint32_t &kb,
                                                   uint32_t &ke)
 {
-    if (!AL)
-        return ilv_slot(p, len, q, o0, kb, ke);
-    o0 = (int32_t)(q * 16u);
-    if (o0 >= (int32_t)len)
-        return false;
-    kb = 0u;
-    ke = len - q * 16u < 16u ? len - q * 16u : 16u;
-    return true;
-}
-
-static __device__ __forceinline__ void plane_store16(uint8_t *p, int32_t o0, uint32_t kb, uint32_t ke, const uint32_t w[4])
-{
-    if (kb == 0u && ke == 16u) {
-        *reinterpret_cast<uint4 *>(p + o0) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 16u; k++)
-            if (k >= kb && k < ke)
-                p[o0 + (int32_t)k] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
-    }
+    return AL ? slot16_part_aligned(len, q, o0, kb, ke) : slot16_part(p, len, q, o0, kb, ke);
 }
 
 template <bool AL> __global__ __launch_bounds__(RS_PLANE_THREADS) void rs_plane_gather_k(RsPlaneArgs a)
@@ -120,105 +86,52 @@ template <bool AL> __global__ __launch_bounds__(RS_PLANE_THREADS) void rs_plane_
     if (t0 >= a.count)
         return;
     const uint32_t tc = a.count - t0 < a.tile ? (uint32_t)(a.count - t0) : a.tile;
-    const uint32_t s = a.tile / 16u + (AL ? 0u : 1u), total = a.w * s;
-    for (uint32_t base = threadIdx.x; base < total; base += RS_PLANE_THREADS * RS_PLANE_BATCH) {
-        uint4 v[RS_PLANE_BATCH];
-        uint32_t col[RS_PLANE_BATCH], kb[RS_PLANE_BATCH], ke[RS_PLANE_BATCH];
-        int32_t o0[RS_PLANE_BATCH];
-#pragma unroll
-        for (uint32_t u = 0; u < RS_PLANE_BATCH; u++) {
-            const uint32_t i = base + u * RS_PLANE_THREADS;
-            kb[u] = ke[u] = 0u;
-            o0[u] = 0;
-            col[u] = 0u;
-            v[u] = make_uint4(0u, 0u, 0u, 0u);
-            if (i >= total)
-                continue;
+    const uint32_t s = a.tile / 16u + (AL ? 0u : 1u);
+    /* item i -> plane j = i / s (the tag), slot q = i mod s; a plane that is not read gives zeros */
+    slot16_batched<RS_PLANE_THREADS, RS_PLANE_BATCH>(
+        a.w * s,
+        [&](uint32_t i, Slot16 &sl, uint4 &v) {
             uint32_t j, q;
-            plane_item(i, s, a.inv, j, q);
-            col[u] = j;
+            slot16_divmod(i, s, a.inv, j, q);
+            sl.tag = j;
             const uint8_t *p = nullptr;
             if (j >= a.first && j < a.last && !((a.lost[j >> 5] >> (j & 31u)) & 1u) && a.plane[j])
                 p = a.plane[j] + a.base + t0;
-            if (!plane_slot<AL>(p, tc, q, o0[u], kb[u], ke[u]))
-                kb[u] = ke[u] = 0u;
-            else if (p)
-                v[u] = ilv_load16(p, o0[u], kb[u], ke[u]);
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < RS_PLANE_BATCH; u++) {
-            if (kb[u] >= ke[u])
-                continue;
-            const uint32_t x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-            uint8_t *c = img + o0[u] * (int32_t)a.w + (int32_t)col[u]; /* o0 < 0 only with kb > 0 */
-            if (kb[u] == 0u && ke[u] == 16u) { /* nearly every slot: sixteen stores and no branch */
-#pragma unroll
-                for (uint32_t k = 0; k < 16u; k++)
-                    c[(int32_t)(k * a.w)] = (uint8_t)(x[k >> 2] >> (8u * (k & 3u)));
-            } else {
-#pragma unroll
-                for (uint32_t k = 0; k < 16u; k++)
-                    if (k >= kb[u] && k < ke[u])
-                        c[(int32_t)(k * a.w)] = (uint8_t)(x[k >> 2] >> (8u * (k & 3u)));
-            }
-        }
-    }
+            if (plane_slot<AL>(p, tc, q, sl.o0, sl.kb, sl.ke))
+                v = p ? slot16_load(p, sl.o0, sl.kb, sl.ke) : make_uint4(0u, 0u, 0u, 0u);
+        },
+        [&](const Slot16 &sl, const uint4 &v) {
+            const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+            /* down column j of the image; o0 < 0 only with kb > 0 */
+            slot16_spread(img + sl.o0 * (int32_t)a.w + (int32_t)sl.tag, (int32_t)a.w, x, sl.kb, sl.ke);
+        });
     __syncthreads();
-    uint8_t *run = a.rows + t0 * a.w;
-    const uint32_t len = tc * a.w;
-    for (uint32_t q = threadIdx.x; q * 16u < len; q += RS_PLANE_THREADS) {
-        if (q * 16u + 16u <= len) {
-            reinterpret_cast<uint4 *>(run)[q] = plane_lds[q];
-        } else {
-            for (uint32_t b = q * 16u; b < len; b++)
-                run[b] = img[b];
-        }
-    }
+    slot16_image_out<RS_PLANE_THREADS>(a.rows + t0 * a.w, tc * a.w, plane_lds);
 }
 
 template <bool AL> __global__ __launch_bounds__(RS_PLANE_THREADS) void rs_plane_scatter_k(RsPlaneArgs a)
 {
     extern __shared__ uint4 plane_lds[];
-    uint8_t *img = reinterpret_cast<uint8_t *>(plane_lds);
+    const uint8_t *img = reinterpret_cast<const uint8_t *>(plane_lds);
     const size_t t0 = (size_t)blockIdx.x * a.tile;
     if (t0 >= a.count)
         return;
     const uint32_t tc = a.count - t0 < a.tile ? (uint32_t)(a.count - t0) : a.tile;
-    const uint8_t *run = a.rows + t0 * a.w;
-    const uint32_t len = tc * a.w;
-    for (uint32_t q = threadIdx.x; q * 16u < len; q += RS_PLANE_THREADS) {
-        if (q * 16u + 16u <= len) {
-            plane_lds[q] = reinterpret_cast<const uint4 *>(run)[q];
-        } else {
-            for (uint32_t b = q * 16u; b < len; b++)
-                img[b] = run[b];
-        }
-    }
+    slot16_image_in<RS_PLANE_THREADS>(plane_lds, a.rows + t0 * a.w, tc * a.w);
     __syncthreads();
     const uint32_t s = a.tile / 16u + (AL ? 0u : 1u), total = (a.last - a.first) * s;
     for (uint32_t i = threadIdx.x; i < total; i += RS_PLANE_THREADS) {
-        uint32_t j, q, kb, ke;
+        uint32_t j, q, kb, ke, x[4];
         int32_t o0;
-        plane_item(i, s, a.inv, j, q);
+        slot16_divmod(i, s, a.inv, j, q);
         j += a.first;
         if (!a.plane[j])
             continue;
         uint8_t *p = a.plane[j] + a.base + t0;
         if (!plane_slot<AL>(p, tc, q, o0, kb, ke))
             continue;
-        const uint8_t *c = img + o0 * (int32_t)a.w + (int32_t)j;
-        uint32_t x[4] = {0u, 0u, 0u, 0u};
-        if (kb == 0u && ke == 16u) { /* sixteen loads in flight and no branch */
-#pragma unroll
-            for (uint32_t k = 0; k < 16u; k++)
-                x[k >> 2] |= (uint32_t)c[(int32_t)(k * a.w)] << (8u * (k & 3u));
-        } else {
-#pragma unroll
-            for (uint32_t k = 0; k < 16u; k++)
-                if (k >= kb && k < ke)
-                    x[k >> 2] |= (uint32_t)c[(int32_t)(k * a.w)] << (8u * (k & 3u));
-        }
-        plane_store16(p, o0, kb, ke, x);
+        slot16_collect(x, img + o0 * (int32_t)a.w + (int32_t)j, (int32_t)a.w, kb, ke);
+        slot16_store(p, o0, kb, ke, x);
     }
 }
 

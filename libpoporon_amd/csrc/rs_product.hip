@@ -119,27 +119,12 @@ static __device__ __forceinline__ bool prod_tile(const RsProdArgs &a, RsProdTile
     return true;
 }
 
-/* i / d and i mod d for i < 2^24 (exact in float), inv = 1 / d: the estimate is off by at most one */
-static __device__ __forceinline__ void prod_div(uint32_t i, uint32_t d, float inv, uint32_t &quo, uint32_t &rem)
-{
-    quo = (uint32_t)((float)i * inv);
-    int32_t r = (int32_t)(i - quo * d);
-    if (r < 0) {
-        r += (int32_t)d;
-        quo--;
-    } else if (r >= (int32_t)d) {
-        r -= (int32_t)d;
-        quo++;
-    }
-    rem = (uint32_t)r;
-}
-
 /* run r of the tile: its address in the blocks, and where its byte 0 lies in the image; byte k lies `step` further */
 static __device__ __forceinline__ uint8_t *prod_run(const RsProdArgs &a, const RsProdTile &t, uint32_t r, float inv_rpb,
                                                     uint32_t &img0)
 {
     uint32_t bb, x;
-    prod_div(r, t.rpb, inv_rpb, bb, x);
+    slot16_divmod(r, t.rpb, inv_rpb, bb, x);
     uint8_t *blk = a.blocks + (t.b0 + bb) * a.bstride;
     if (a.axis) {
         img0 = bb * a.cw * a.w + a.m0 + x;
@@ -157,64 +142,27 @@ __global__ __launch_bounds__(RS_PROD_THREADS) void rs_prod_gather_k(RsProdArgs a
         return;
     uint8_t *img = reinterpret_cast<uint8_t *>(prod_lds) + t.head;
     const int32_t step = a.axis ? (int32_t)a.w : 1;
-    const uint32_t total = t.nr * a.s;
     const float inv_nr = 1.0f / (float)t.nr, inv_rpb = 1.0f / (float)t.rpb;
-    for (uint32_t base = threadIdx.x; base < total; base += RS_PROD_THREADS * RS_PROD_BATCH) {
-        uint4 v[RS_PROD_BATCH];
-        uint32_t at[RS_PROD_BATCH], kb[RS_PROD_BATCH], ke[RS_PROD_BATCH];
-        int32_t o0[RS_PROD_BATCH];
-#pragma unroll
-        for (uint32_t n = 0; n < RS_PROD_BATCH; n++) {
-            const uint32_t i = base + n * RS_PROD_THREADS;
-            kb[n] = ke[n] = 0u;
-            o0[n] = 0;
-            at[n] = 0u;
-            v[n] = make_uint4(0u, 0u, 0u, 0u);
-            if (i >= total)
-                continue;
+    /* item i -> slot q = i / nr of run r = i mod nr; the tag is where the run's byte 0 lies in the image */
+    slot16_batched<RS_PROD_THREADS, RS_PROD_BATCH>(
+        t.nr * a.s,
+        [&](uint32_t i, Slot16 &sl, uint4 &v) {
             uint32_t q, r;
-            prod_div(i, t.nr, inv_nr, q, r);
-            const uint8_t *p = prod_run(a, t, r, inv_rpb, at[n]);
-            if (!ilv_slot(p, t.len, q, o0[n], kb[n], ke[n]))
-                kb[n] = ke[n] = 0u;
-            else if (p + o0[n] >= a.blocks && p + o0[n] + 16 <= a.blocks + a.span)
-                v[n] = *reinterpret_cast<const uint4 *>(p + o0[n]); /* a head or tail slot inside the blocks: whole */
+            slot16_divmod(i, t.nr, inv_nr, q, r);
+            const uint8_t *p = prod_run(a, t, r, inv_rpb, sl.tag);
+            if (!slot16_part(p, t.len, q, sl.o0, sl.kb, sl.ke))
+                return;
+            if (p + sl.o0 >= a.blocks && p + sl.o0 + 16 <= a.blocks + a.span)
+                v = *reinterpret_cast<const uint4 *>(p + sl.o0); /* a head or tail slot inside the blocks: whole */
             else
-                v[n] = ilv_load16(p, o0[n], kb[n], ke[n]);
-        }
-#pragma unroll
-        for (uint32_t n = 0; n < RS_PROD_BATCH; n++) {
-            if (kb[n] >= ke[n])
-                continue;
-            const uint32_t x[4] = {v[n].x, v[n].y, v[n].z, v[n].w};
-            uint8_t *c = img + (int32_t)at[n] + o0[n] * step; /* o0 < 0 only with kb > 0 */
-            if (kb[n] == 0u && ke[n] == 16u) {
-#pragma unroll
-                for (int32_t k = 0; k < 16; k++)
-                    c[k * step] = (uint8_t)(x[k >> 2] >> (8 * (k & 3)));
-            } else {
-#pragma unroll
-                for (int32_t k = 0; k < 16; k++)
-                    if ((uint32_t)k >= kb[n] && (uint32_t)k < ke[n])
-                        c[k * step] = (uint8_t)(x[k >> 2] >> (8 * (k & 3)));
-            }
-        }
-    }
+                v = slot16_load(p, sl.o0, sl.kb, sl.ke);
+        },
+        [&](const Slot16 &sl, const uint4 &v) {
+            const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+            slot16_spread(img + (int32_t)sl.tag + sl.o0 * step, step, x, sl.kb, sl.ke); /* o0 < 0 only with kb > 0 */
+        });
     __syncthreads();
-    uint8_t *run = a.rows + t.off;
-    const uint8_t *lds = reinterpret_cast<const uint8_t *>(prod_lds);
-    for (uint32_t q = threadIdx.x; q * 16u < t.head + t.bytes; q += RS_PROD_THREADS) {
-        int32_t o0;
-        uint32_t kb, ke;
-        if (!ilv_slot(run, t.bytes, q, o0, kb, ke))
-            continue;
-        if (kb == 0u && ke == 16u) {
-            *reinterpret_cast<uint4 *>(run + o0) = prod_lds[q];
-        } else {
-            for (uint32_t k = kb; k < ke; k++)
-                run[o0 + (int32_t)k] = lds[q * 16u + k];
-        }
-    }
+    slot16_image_out<RS_PROD_THREADS>(a.rows + t.off, t.bytes, prod_lds);
 }
 
 __global__ __launch_bounds__(RS_PROD_THREADS) void rs_prod_scatter_k(RsProdArgs a)
@@ -223,33 +171,22 @@ __global__ __launch_bounds__(RS_PROD_THREADS) void rs_prod_scatter_k(RsProdArgs 
     RsProdTile t;
     if (!prod_tile(a, t))
         return;
-    const uint8_t *run = a.rows + t.off;
-    uint8_t *lds = reinterpret_cast<uint8_t *>(prod_lds);
-    for (uint32_t q = threadIdx.x; q * 16u < t.head + t.bytes; q += RS_PROD_THREADS) {
-        int32_t o0;
-        uint32_t kb, ke;
-        if (!ilv_slot(run, t.bytes, q, o0, kb, ke))
-            continue;
-        if (kb == 0u && ke == 16u) {
-            prod_lds[q] = *reinterpret_cast<const uint4 *>(run + o0);
-        } else {
-            for (uint32_t k = kb; k < ke; k++)
-                lds[q * 16u + k] = run[o0 + (int32_t)k];
-        }
-    }
+    slot16_image_in<RS_PROD_THREADS>(prod_lds, a.rows + t.off, t.bytes);
     __syncthreads();
-    const uint8_t *img = lds + t.head;
+    const uint8_t *img = reinterpret_cast<const uint8_t *>(prod_lds) + t.head;
     const int32_t step = a.axis ? (int32_t)a.w : 1;
     const uint32_t total = t.nr * a.s;
     const float inv_nr = 1.0f / (float)t.nr, inv_rpb = 1.0f / (float)t.rpb;
     for (uint32_t i = threadIdx.x; i < total; i += RS_PROD_THREADS) {
         uint32_t q, r, at, kb, ke;
         int32_t o0;
-        prod_div(i, t.nr, inv_nr, q, r);
+        slot16_divmod(i, t.nr, inv_nr, q, r);
         uint8_t *p = prod_run(a, t, r, inv_rpb, at);
-        if (!ilv_slot(p, t.len, q, o0, kb, ke))
+        if (!slot16_part(p, t.len, q, o0, kb, ke))
             continue;
         const uint8_t *c = img + (int32_t)at + o0 * step;
+        /* the collect is written out here, each branch ending in its own store: through slot16_collect this kernel
+         * measured 3 to 8 % slower */
         uint32_t x[4] = {0u, 0u, 0u, 0u};
         if (kb == 0u && ke == 16u) { /* sixteen loads in flight and no branch */
 #pragma unroll

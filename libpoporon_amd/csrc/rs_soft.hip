@@ -63,9 +63,9 @@ static __device__ __forceinline__ void soft_load_llr(uint8_t *dst, const uint8_t
     for (uint32_t q = lane; q < slots; q += 64u) {
         int32_t o0;
         uint32_t kb, ke;
-        if (!ilv_slot(p, len, q, o0, kb, ke))
+        if (!slot16_part(p, len, q, o0, kb, ke))
             continue;
-        const uint4 v = ilv_load16(p, o0, kb, ke);
+        const uint4 v = slot16_load(p, o0, kb, ke);
         if (head == 0u && kb == 0u && ke == 16u) {
             *reinterpret_cast<uint4 *>(dst + o0) = v;
         } else {

@@ -157,7 +157,7 @@ def _div(i, d):
 
 
 def _slots(addr, length, q):
-    """ilv_slot for arrays: slot q of runs of `length` bytes at addr -> (o0, kb, ke, valid)"""
+    """slot16_part for arrays: slot q of runs of `length` bytes at addr -> (o0, kb, ke, valid)"""
     o0 = 16 * q - (addr & 15)
     kb = np.where(o0 < 0, -o0, 0)
     ke = np.minimum(16, length - o0)
