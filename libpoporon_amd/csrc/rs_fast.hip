@@ -147,7 +147,7 @@ __global__ __launch_bounds__(BWG, BM_WAVES) void rs_bm_k(const RsDevTables *__re
          * each, taken once per iteration for the discrepancy and B's copy: 3
          * lookups per term instead of 4.  B (address-form logs) and the
          * syndrome window one register per entry: no half-word extractions
-         * (103 VGPRs, 4 waves/SIMD) */
+         * (100 VGPRs, 4 waves/SIMD) */
         const uint32_t HZ = pofs + 1u; /* hl of a zero coefficient */
         uint32_t hl[NL], B[NL + 1];
         hl[0] = HZ + 128u;
@@ -158,8 +158,11 @@ __global__ __launch_bounds__(BWG, BM_WAVES) void rs_bm_k(const RsDevTables *__re
 #pragma unroll
         for (int k = 1; k <= NL; ++k)
             B[k] = AZ;
-        uint32_t dl = 0, db = 0, L = 0, lb = 0, ubp = 0;
-        uint32_t over = 0, bo = 0; /* 0 / 1 */
+        /* dl, D: the degree bounds of Lambda and of x B (D = db + 1); L2 = 2L;
+         * lbp: the address-form log of the discrepancy of the last lengthening
+         * (b's log plus pofs: only differences of such logs are taken) */
+        uint32_t dl = 0, D = 1, L2 = 0, lbp = pofs, ubp = 0;
+        uint64_t overm = 0, bom = 0; /* over / bo, one bit per lane */
         uint32_t WL[20];
 #pragma unroll
         for (int k = 0; k < 20; ++k)
@@ -169,15 +172,14 @@ __global__ __launch_bounds__(BWG, BM_WAVES) void rs_bm_k(const RsDevTables *__re
         auto step = [&](auto sc, uint32_t r) __attribute__((always_inline)) {
             constexpr int s = decltype(sc)::value;
             const uint32_t ub = ubp;
+            /* la_i = log Lambda_i for the groups up to ub; the groups past it
+             * are zero and not formed (the one the B select can reach is set
+             * to AZ there) */
             uint32_t la[NL];
             uint32_t disc = 0;
             la[0] = pofs;
 #pragma unroll
             for (int g = 0; g < NL; g += 4) {
-#pragma unroll
-                for (int i = g; i < g + 4 && i < NL; ++i)
-                    if (i > 0)
-                        la[i] = AZ;
                 if ((uint32_t)g <= ub) {
 #pragma unroll
                     for (int i = g; i < g + 4 && i < NL; ++i) {
@@ -187,30 +189,63 @@ __global__ __launch_bounds__(BWG, BM_WAVES) void rs_bm_k(const RsDevTables *__re
                     }
                 }
             }
-            const uint32_t ld = gf.logs(disc);
-            const bool upd = disc != 0u;
-            const bool lengthen = upd && (2u * L <= r - 1u);
-            const int32_t dd = (int32_t)ld - (int32_t)lb;
-            const uint32_t dq = upd ? (uint32_t)(dd < 0 ? dd + 255 * 128 : dd) : DQZ;
-            const uint32_t b16 = B[NL - 1] != AZ;
-            over |= upd ? (bo | b16) : 0u;
-            bo = lengthen ? 0u : (bo | b16);
-            /* (formed before the discrepancy instead, to overlap its lookups:
-             * unchanged, profiles/r04_bm_hoist_ab.log) */
-            const uint32_t up = min((uint32_t)(NL - 1), max(dl, db + 1u));
-            const uint32_t ub2 = wave_max_full(up);
+            /* The per-iteration state in full-rate forms: wave masks in
+             * SGPRs for upd / lengthen / over / bo, 16-bit min / max / modular
+             * subtract, selects on VCC (an e64 select on an SGPR mask, a
+             * 32-bit min or max and a 32-bit left shift issue at half rate) */
+            const uint32_t ld = lds16(HZ + shl7(disc)); /* address-form log of the discrepancy */
+            const uint64_t updm = __ballot(disc != 0u);
+            const uint64_t lmask = updm & __ballot(L2 < r); /* lengthen: upd && 2L <= r - 1 */
+            const uint64_t b16m = bom | __ballot(B[NL - 1] != AZ);
+            overm |= updm & b16m;
+            bom = b16m & ~lmask;
+            /* (up formed before the discrepancy instead, to overlap its
+             * lookups: unchanged, profiles/r04_bm_hoist_ab.log) */
+            const uint32_t cD = min16_u16(D);
+            const uint32_t up = max_u16(dl, cD); /* min(16, max(dl, db + 1)) */
+            /* its wave maximum: up never falls and rises by at most one per
+             * iteration in every lane (dl <- up, db + 1 <- min(db + 2, 16) or
+             * dl + 1 <= up + 1), so the maximum is ub or ub + 1.  This needs
+             * every lane of the wave in every step (no step under a divergent
+             * exec: the ballot must see all 64) and ubp to be the exact maximum
+             * of the iteration before (0 at the start, where up = 1) */
+            const uint32_t ub2 = ub + (__ballot(up > ub) != 0ull ? 1u : 0u);
             ubp = ub2;
-            const uint64_t lmask = __ballot(lengthen);
+            const uint32_t dq0 = submod7(ld, lbp);
+            const uint32_t nl2 = 2u * r - L2;
+            uint32_t dq, dn;
+            asm("s_mov_b64 vcc, %[lm]\n\t"
+                "v_cndmask_b32_e32 %[dn], %[cd], %[dl], vcc\n\t"
+                "v_cndmask_b32_e32 %[l2], %[l2], %[nl2], vcc\n\t"
+                "v_cndmask_b32_e32 %[lbp], %[lbp], %[ld], vcc\n\t"
+                "s_mov_b64 vcc, %[um]\n\t"
+                "v_cndmask_b32_e32 %[dq], %[dqz], %[dq0], vcc\n\t"
+                "v_cndmask_b32_e32 %[dl], %[dl], %[up], vcc"
+                : [dn] "=&v"(dn), [l2] "+v"(L2), [lbp] "+v"(lbp), [dq] "=&v"(dq), [dl] "+v"(dl)
+                : [cd] "v"(cD), [nl2] "v"(nl2), [ld] "v"(ld), [dq0] "v"(dq0), [up] "v"(up), [dqz] "v"(DQZ),
+                  [lm] "s"(lmask), [um] "s"(updm)
+                : "vcc");
+            D = dn + 1u; /* db <- lengthen ? dl (old) : min(db + 1, 16) */
+            /* B_i <- lengthen ? log Lambda_i (old) : B_(i-1) group by group, top
+             * down, as VOP2 selects on VCC (2 % over the compiler's e64
+             * selects, profiles/r03_bm_vccsel.log) */
             static_for<0, (NL - 1) / 4 + 1, 1>([&](auto mc) __attribute__((always_inline)) {
                 constexpr int m = (NL - 1) / 4 - decltype(mc)::value; /* top down */
+                const uint64_t lm = lmask; /* (an asm operand alone does not capture it) */
                 if ((uint32_t)(4 * m) <= ub2) {
 #pragma unroll
                     for (int i = 4 * m + 3; i >= 4 * m; --i)
                         if (i > 0 && i < NL)
                             hl[i] ^= shl7(gf.expa(dq + B[i - 1]));
-                    /* B_i <- lengthen ? log Lambda_i (old) : B_(i-1), top down,
-                     * as VOP2 selects on VCC (the compiler's e64 selects on an
-                     * SGPR mask issue at half rate; 2 %, profiles/r03_bm_vccsel.log) */
+                    /* la of this group was formed above iff 4m <= ub; since ub2 is
+                     * ub or ub + 1 (above), the only other group that gets here is
+                     * 4m = ub2 = ub + 1, whose Lambda is zero.  Were ub2 ever to
+                     * exceed ub + 1, this would still set every group reached */
+                    if ((uint32_t)(4 * m) > ub) {
+#pragma unroll
+                        for (int i = 4 * m; i < 4 * m + 4 && i < NL; ++i)
+                            la[i] = AZ;
+                    }
                     if constexpr (4 * m + 3 < NL) {
                         const uint32_t b0 = m > 0 ? B[m > 0 ? 4 * m - 1 : 0] : AZ;
                         asm("s_mov_b64 vcc, %8\n\t"
@@ -220,20 +255,17 @@ __global__ __launch_bounds__(BWG, BM_WAVES) void rs_bm_k(const RsDevTables *__re
                             "v_cndmask_b32_e32 %0, %9, %4, vcc"
                             : "+v"(B[4 * m]), "+v"(B[4 * m + 1]), "+v"(B[4 * m + 2]), "+v"(B[4 * m + 3])
                             : "v"(la[4 * m]), "v"(la[4 * m + 1]), "v"(la[4 * m + 2]), "v"(la[4 * m + 3]),
-                              "s"(lmask), "v"(b0)
+                              "s"(lm), "v"(b0)
                             : "vcc");
-                    } else {
-                        B[4 * m] = lengthen ? la[4 * m] : B[4 * m - 1]; /* B_16; B_17 plays no part */
+                    } else { /* B_16; B_17 plays no part */
+                        asm("s_mov_b64 vcc, %3\n\t"
+                            "v_cndmask_b32_e32 %0, %1, %2, vcc"
+                            : "=v"(B[4 * m])
+                            : "v"(B[4 * m - 1]), "v"(la[4 * m]), "s"(lm)
+                            : "vcc");
                     }
                 }
             });
-            db = lengthen ? dl : min(db + 1u, (uint32_t)(NL - 1));
-            if (upd)
-                dl = up;
-            if (lengthen) {
-                L = r - L;
-                lb = ld;
-            }
         };
         const uint32_t nq = NRG ? (npar + 3u) >> 2 : RS_NR / 4;
 #pragma unroll 1
@@ -267,7 +299,8 @@ __global__ __launch_bounds__(BWG, BM_WAVES) void rs_bm_k(const RsDevTables *__re
 #pragma unroll
         for (int i = 0; i < NL; ++i)
             deg = (al[i] & 1u) ? (uint32_t)i : deg;
-        const bool fast = any && !over && deg == L && deg != 0u && (!NRG || 2u * L <= npar);
+        const bool over = (overm >> (threadIdx.x & 63u)) & 1ull;
+        const bool fast = any && !over && 2u * deg == L2 && deg != 0u && (!NRG || L2 <= npar);
 
         /* ---- Omega = S * Lambda mod x^deg (log form), src/decode.c:147-158 ---- */
         uint32_t ob[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};

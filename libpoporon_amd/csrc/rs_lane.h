@@ -67,6 +67,33 @@ __device__ __forceinline__ uint32_t addmod7(uint32_t x, uint32_t y)
     return r;
 }
 
+/* (x - y) mod 255 * 128 for two values whose difference is that of two scaled
+ * logs < 255 * 128 (plain or address-form alike): the same three full-rate
+ * 16-bit ops -- a borrow wraps t above t + 255 * 128 */
+__device__ __forceinline__ uint32_t submod7(uint32_t x, uint32_t y)
+{
+    uint32_t t, u, r;
+    asm("v_sub_u16 %0, %1, %2" : "=v"(t) : "v"(x), "v"(y));
+    asm("v_add_u16 %0, 0x7f80, %1" : "=v"(u) : "v"(t));
+    asm("v_min_u16 %0, %1, %2" : "=v"(r) : "v"(t), "v"(u));
+    return r;
+}
+
+/* min(16, a) and max(a, b) of values < 2^16 at full rate (v_min_u32 and
+ * v_max_u32 issue at half rate: profiles/r02_valu_rate_probe.log) */
+__device__ __forceinline__ uint32_t min16_u16(uint32_t a)
+{
+    uint32_t r;
+    asm("v_min_u16 %0, 16, %1" : "=v"(r) : "v"(a));
+    return r;
+}
+__device__ __forceinline__ uint32_t max_u16(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("v_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
 /* Persistent loops: issue priority falling with the wave's progress (it =
  * batches done), so the waves that are behind win the issue arbitration
  * (priority, then age) and a workgroup's waves finish together instead of
