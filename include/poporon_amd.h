@@ -699,6 +699,89 @@ bool poporon_decode_soft_batch_device(poporon_t *pprn, const int8_t *d_llr, size
                                       size_t count, unsigned flips, uint8_t *d_ok, uint8_t *d_changed,
                                       uint8_t *d_pattern, uint32_t *d_score, void *stream);
 
+/* ---- K = 7 convolutional code: batch encode and Viterbi decode ----------------
+ * The inner code of the DVB-S / DVB-T and CCSDS 131.0-B chains: constraint
+ * length 7, rate 1/2, punctured by a periodic pattern.  The decoder's output is
+ * what poporon_decode_conv_device takes.  Everything is integer arithmetic and
+ * pinned here, so the result is defined bit for bit (tests/cc_ref.py is the
+ * model).  The handle holds parameters only: no device memory, no reserve call,
+ * no kernel-timing id.  Calls run on the current HIP device, asynchronously on
+ * `stream`.  There is no host form.
+ *
+ * Code.  A state is 6 bits, the last six input bits, newest at bit 5.  For
+ * input bit u in state s the register is r = (u << 6) | s; output j is
+ * parity(r & g_j) ^ ((invert >> j) & 1); the next state is r >> 1.  g0, g1 in
+ * [1, 127], invert in [0, 3].  CCSDS is (0171, 0133, invert 2), DVB
+ * (0171, 0133, 0).
+ *
+ * Puncturing.  Step t has phase t % period (period in [1, 16]).  Output 0 of
+ * the step is transmitted iff bit `phase` of keep0 is set, output 1 likewise by
+ * keep1; a step's kept outputs go out in the order 0, 1.  The masks have no bit
+ * at or above `period` and at least one bit between them; a phase that keeps
+ * nothing is allowed.  poporon_amd_cc_symbols(nbits) is the number of kept
+ * symbols of nbits steps.
+ *
+ * Bit packing (info bits and the encoder's symbols).  Bit t of a frame is bit
+ * 7 - t % 8 of byte t / 8 (MSB first); the spare low bits of a frame's last
+ * byte are written as 0; no byte past ceil(n / 8) of a frame is written.
+ *
+ * Encode.  Frame c reads nbits bits at d_bits + c*bits_stride, starts in
+ * start_state (0..63) and writes poporon_amd_cc_symbols(nbits) packed hard
+ * symbols at d_symbols + c*symbols_stride; d_end_state[c] (may be NULL) gets
+ * the final state.
+ *
+ * Decode input.  Frame c has M = poporon_amd_cc_symbols(nbits) int8 values at
+ * d_llr + c*llr_stride, kept symbols only.  Negative means 1, 0 is an erasure.
+ * Hypothesising bit b for the received value v costs |v| (-128 gives 128) if
+ * v != 0 and (v < 0) != b, else 0; punctured outputs cost 0; a path metric is
+ * the sum of the costs along the path.
+ *
+ * Decode blocks.  B = block, V = overlap.  Block b emits the steps
+ * [bB, min(nbits, (b+1)B)) from the window [t0, t1) = [max(0, bB - V),
+ * min(nbits, (b+1)B + V)); blocks are independent.
+ *  - Initial metrics at t0: if t0 == 0 and start_state >= 0 only paths that
+ *    start in start_state exist; otherwise all 64 states start at 0.
+ *  - Add-compare-select: the predecessors of state s' are ((s' << 1) | d) & 63
+ *    for d = 0, 1, the hypothesised input is s' >> 5, the smaller metric
+ *    survives, a tie goes to d = 0.
+ *  - End at t1: if t1 == nbits and end_state >= 0 the traceback starts in
+ *    end_state, otherwise in the state of least metric, ties to the lowest
+ *    state number.
+ *  - Output: the bit of step t is bit 5 of the path's state after step t; only
+ *    the block's own steps are written.  d_metric[c*blocks + b] (may be NULL;
+ *    blocks = poporon_amd_cc_blocks(nbits) = ceil(nbits / B)) gets the metric of
+ *    the state the traceback started in.
+ * An end_state that cannot be reached from start_state in nbits < 6 steps is
+ * the caller's error: those bits are unspecified but stay inside the frame.
+ *
+ * Create fails, with a message, for polynomials, inversion or masks outside the
+ * above, block not a multiple of 64 in [64, 4096] and overlap > 1024; block = 0
+ * and overlap = 0xFFFFFFFF select the library defaults (512 and 96: DESIGN
+ * section 19 has the measurements behind them).  The calls fail before they
+ * touch the GPU for a NULL handle, nbits == 0, a state outside 0..63 (encode
+ * start) or -1..63 (decode), strides smaller than a frame (bits: ceil(nbits/8),
+ * symbols: ceil(M/8), LLRs: M) and NULL d_bits, d_symbols or d_llr.  count == 0
+ * returns true without touching the GPU.  Bases and strides may have any
+ * alignment; symbol and bit offsets are 64-bit.
+ *
+ * How (cc.hip): a decode is one wave per block, lane = state; count * blocks
+ * waves go out in launches of at most POPORON_AMD_CC_CHUNK blocks (environment,
+ * read at create; default 2^22), an encode in launches of 64 times as many
+ * threads, one thread per 32 symbols. */
+typedef struct _poporon_cc_t poporon_cc_t;
+
+poporon_cc_t *poporon_amd_cc_create(unsigned g0, unsigned g1, unsigned invert, unsigned period, uint32_t keep0,
+                                    uint32_t keep1, unsigned block, unsigned overlap);
+void poporon_amd_cc_destroy(poporon_cc_t *cc);
+size_t poporon_amd_cc_symbols(const poporon_cc_t *cc, size_t nbits);
+size_t poporon_amd_cc_blocks(const poporon_cc_t *cc, size_t nbits);
+bool poporon_cc_encode_device(const poporon_cc_t *cc, const uint8_t *d_bits, size_t bits_stride, size_t nbits,
+                              size_t count, int start_state, uint8_t *d_symbols, size_t symbols_stride,
+                              uint8_t *d_end_state, void *stream);
+bool poporon_cc_decode_device(const poporon_cc_t *cc, const int8_t *d_llr, size_t llr_stride, size_t nbits,
+                              size_t count, int start_state, int end_state, uint8_t *d_bits, size_t bits_stride,
+                              uint32_t *d_metric, void *stream);
+
 /* ---- LDPC batches -----------------------------------------------------------
  * Row c has info_bytes (poporon_get_info_size) of data at d_data +
  * c*data_stride and parity_bytes (poporon_get_parity_size) of parity at

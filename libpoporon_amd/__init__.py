@@ -161,6 +161,15 @@ _SIGS = {
     "poporon_encode_product": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
     "poporon_decode_product": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                           C.c_int, C.c_size_t, C.c_int, _vp, _vp, _vp]),
+    "poporon_amd_cc_create": (_vp, [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint32, C.c_uint32, C.c_uint,
+                                    C.c_uint]),
+    "poporon_amd_cc_destroy": (None, [_vp]),
+    "poporon_amd_cc_symbols": (C.c_size_t, [_vp, C.c_size_t]),
+    "poporon_amd_cc_blocks": (C.c_size_t, [_vp, C.c_size_t]),
+    "poporon_cc_encode_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _vp, C.c_size_t,
+                                            _vp, _vp]),
+    "poporon_cc_decode_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _vp,
+                                            C.c_size_t, _vp, _vp]),
     "poporon_rng_create": (_vp, [C.c_int, _vp, C.c_size_t]),
     "poporon_rng_destroy": (None, [_vp]),
     "poporon_rng_next": (C.c_bool, [_vp, _vp, C.c_size_t]),
@@ -1210,6 +1219,68 @@ class Product:
     def close(self):
         if getattr(self, "h", None):
             self.lib.poporon_amd_product_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+# ---- K = 7 convolutional code (include/poporon_amd.h) --------------------------------
+# (g0, g1, invert)
+CC_CODE_CCSDS = (0o171, 0o133, 2)
+CC_CODE_DVB = (0o171, 0o133, 0)
+# (period, keep0, keep1): bit k of a mask is phase k
+CC_PUNCTURE_NONE = (1, 0b1, 0b1)
+CC_PUNCTURE_DVB_2_3 = (2, 0b01, 0b11)
+CC_PUNCTURE_DVB_3_4 = (3, 0b101, 0b011)
+CC_PUNCTURE_DVB_5_6 = (5, 0b10101, 0b01011)
+CC_PUNCTURE_DVB_7_8 = (7, 0b1010001, 0b0101111)
+CC_DEFAULT_BLOCK, CC_DEFAULT_OVERLAP = 0, 0xFFFFFFFF  # the values that select the library defaults
+
+
+def _dptr(a):
+    """a device pointer: an int (None or 0: NULL) or a torch tensor"""
+    if a is None:
+        return None
+    return (a.data_ptr() if hasattr(a, "data_ptr") else int(a)) or None
+
+
+class Cc:
+    """poporon_cc_t (include/poporon_amd.h): the K = 7, rate-1/2 convolutional code with puncturing.  ``code`` is
+    (g0, g1, invert), ``puncture`` (period, keep0, keep1); ``block`` / ``overlap`` are the decoder's B and V.
+    Buffers are device pointers (ints) or torch tensors; bits and symbols are packed MSB first, LLRs are int8."""
+
+    def __init__(self, code=CC_CODE_DVB, puncture=CC_PUNCTURE_NONE, block=CC_DEFAULT_BLOCK,
+                 overlap=CC_DEFAULT_OVERLAP):
+        self.lib = load_library()
+        self.h = self.lib.poporon_amd_cc_create(*code, *puncture, block, overlap)
+        if not self.h:
+            raise PoporonError(f"poporon_amd_cc_create failed: {last_error()}")
+
+    def _check(self, ok, what):
+        if not ok:
+            raise PoporonError(f"{what} failed: {last_error()}")
+
+    def symbols(self, nbits):
+        return int(self.lib.poporon_amd_cc_symbols(self.h, nbits))
+
+    def blocks(self, nbits):
+        return int(self.lib.poporon_amd_cc_blocks(self.h, nbits))
+
+    def encode(self, d_bits, bits_stride, nbits, count, d_symbols, symbols_stride, start_state=0, d_end_state=None,
+               stream=0):
+        self._check(self.lib.poporon_cc_encode_device(self.h, _dptr(d_bits), bits_stride, nbits, count, start_state,
+                                                      _dptr(d_symbols), symbols_stride, _dptr(d_end_state),
+                                                      stream or None), "poporon_cc_encode_device")
+
+    def decode(self, d_llr, llr_stride, nbits, count, d_bits, bits_stride, start_state=-1, end_state=-1,
+               d_metric=None, stream=0):
+        self._check(self.lib.poporon_cc_decode_device(self.h, _dptr(d_llr), llr_stride, nbits, count, start_state,
+                                                      end_state, _dptr(d_bits), bits_stride, _dptr(d_metric),
+                                                      stream or None), "poporon_cc_decode_device")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.poporon_amd_cc_destroy(self.h)
             self.h = None
 
     __del__ = close

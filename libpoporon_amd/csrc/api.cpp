@@ -36,6 +36,7 @@
 #include "bch_device.h"
 #include "ldpc_device.h"
 #include "ldpc_graph.h"
+#include "cc_device.h"
 
 #ifndef POPORON_BUILDTIME
 #define POPORON_BUILDTIME 1
@@ -4402,6 +4403,137 @@ EXPORT bool poporon_decode_product(poporon_product_t *p, uint8_t *blocks, size_t
     const ProdCall c = {FORM_DECODE, blocks, row_pitch, block_stride, row_size,  col_size, count,
                         first_axis,  passes, couple,    row_dirty,    col_dirty, block_ok};
     return prod_host(p, "poporon_decode_product", c);
+}
+
+/* ------------------------------------------------------------------------ */
+/* K = 7 convolutional code: batch encode and blocked Viterbi decode        */
+/* ------------------------------------------------------------------------ */
+
+/*
+ * The handle is the code's parameters and nothing else (cc.hip takes them by
+ * value): no device memory, no streams, no timing.  A decode is count * blocks
+ * waves, an encode count * words threads; either goes out in launches of at
+ * most cc->chunk blocks (64 cc->chunk encode threads), one after another on the
+ * caller's stream, on the current device.
+ */
+/* the fastest setting of tools/cc_bench.py whose errors at rate 7/8 stay inside the seed-to-seed spread of the
+ * overlap = 1024 column */
+#define CC_BLOCK_DEFAULT 512u
+#define CC_OVERLAP_DEFAULT 96u
+#define CC_CHUNK_DEFAULT ((size_t)1 << 22)
+#define CC_CHUNK_MAX ((size_t)1 << 24)
+
+struct _poporon_cc_t {
+    CcParams p;
+    size_t chunk; /* decode blocks per launch (POPORON_AMD_CC_CHUNK) */
+};
+
+EXPORT poporon_cc_t *poporon_amd_cc_create(unsigned g0, unsigned g1, unsigned invert, unsigned period, uint32_t keep0,
+                                           uint32_t keep1, unsigned block, unsigned overlap)
+{
+    const char *what = "poporon_amd_cc_create";
+    if (block == 0u)
+        block = CC_BLOCK_DEFAULT;
+    if (overlap == 0xFFFFFFFFu)
+        overlap = CC_OVERLAP_DEFAULT;
+    bool ok = true;
+    if (g0 < 1u || g0 > 127u || g1 < 1u || g1 > 127u)
+        ok = fail("%s: polynomials %#o, %#o outside [1, 0177]", what, g0, g1);
+    else if (invert > 3u)
+        ok = fail("%s: invert %u > 3", what, invert);
+    else if (period < 1u || period > CC_PERIOD_MAX)
+        ok = fail("%s: period %u outside [1, %u]", what, period, CC_PERIOD_MAX);
+    else if ((keep0 | keep1) >> period)
+        ok = fail("%s: a puncture mask (%#x, %#x) has a bit at or above the period %u", what, keep0, keep1, period);
+    else if (!(keep0 | keep1))
+        ok = fail("%s: the puncture masks keep nothing", what);
+    else if (block % 64u || block < 64u || block > CC_BLOCK_MAX)
+        ok = fail("%s: block %u is no multiple of 64 in [64, %u]", what, block, CC_BLOCK_MAX);
+    else if (overlap > CC_OVERLAP_MAX)
+        ok = fail("%s: overlap %u > %u", what, overlap, CC_OVERLAP_MAX);
+    if (!ok)
+        return nullptr;
+    poporon_cc_t *cc = new (std::nothrow) poporon_cc_t();
+    if (!cc) {
+        fail("%s: out of memory", what);
+        return nullptr;
+    }
+    cc->p = {g0, g1, invert, period, keep0, keep1,
+             (uint32_t)(__builtin_popcount(keep0) + __builtin_popcount(keep1)), block, overlap};
+    const char *ch = getenv("POPORON_AMD_CC_CHUNK");
+    const unsigned long long v = ch ? strtoull(ch, nullptr, 10) : 0ull;
+    cc->chunk = v ? (size_t)std::min<unsigned long long>(v, CC_CHUNK_MAX) : CC_CHUNK_DEFAULT;
+    return cc;
+}
+
+EXPORT void poporon_amd_cc_destroy(poporon_cc_t *cc) { delete cc; }
+
+EXPORT size_t poporon_amd_cc_symbols(const poporon_cc_t *cc, size_t nbits)
+{
+    return cc ? (size_t)cc_symbols_before(cc->p, nbits) : 0;
+}
+
+EXPORT size_t poporon_amd_cc_blocks(const poporon_cc_t *cc, size_t nbits)
+{
+    return cc ? nbits / cc->p.block + (nbits % cc->p.block != 0) : 0;
+}
+
+EXPORT bool poporon_cc_encode_device(const poporon_cc_t *cc, const uint8_t *d_bits, size_t bits_stride, size_t nbits,
+                                     size_t count, int start_state, uint8_t *d_symbols, size_t symbols_stride,
+                                     uint8_t *d_end_state, void *stream)
+{
+    const char *what = "poporon_cc_encode_device";
+    if (!cc)
+        return fail("%s: NULL handle", what);
+    if (nbits == 0)
+        return fail("%s: nbits is 0", what);
+    if (start_state < 0 || start_state > 63)
+        return fail("%s: start_state %d outside [0, 63]", what, start_state);
+    const size_t m = poporon_amd_cc_symbols(cc, nbits), fb = nbits / 8 + (nbits % 8 != 0), sb = m / 8 + (m % 8 != 0);
+    if (bits_stride < fb)
+        return fail("%s: bits_stride %zu < the %zu bytes of a frame", what, bits_stride, fb);
+    if (symbols_stride < sb)
+        return fail("%s: symbols_stride %zu < the %zu bytes of a frame's symbols", what, symbols_stride, sb);
+    if (count == 0)
+        return true;
+    if (!d_bits || !d_symbols)
+        return fail("%s: NULL argument", what);
+    const uint64_t words = std::max<uint64_t>(1, m / 32 + (m % 32 != 0)), total = words * count;
+    const uint64_t per = (uint64_t)cc->chunk * CC_STATES;
+    for (uint64_t first = 0; first < total; first += per)
+        HIP_OK(cck_encode(&cc->p, d_bits, bits_stride, nbits, m, words, first, std::min(per, total - first), start_state,
+                          d_symbols, symbols_stride, d_end_state, static_cast<hipStream_t>(stream)));
+    return true;
+}
+
+EXPORT bool poporon_cc_decode_device(const poporon_cc_t *cc, const int8_t *d_llr, size_t llr_stride, size_t nbits,
+                                     size_t count, int start_state, int end_state, uint8_t *d_bits, size_t bits_stride,
+                                     uint32_t *d_metric, void *stream)
+{
+    const char *what = "poporon_cc_decode_device";
+    if (!cc)
+        return fail("%s: NULL handle", what);
+    if (nbits == 0)
+        return fail("%s: nbits is 0", what);
+    if (start_state < -1 || start_state > 63)
+        return fail("%s: start_state %d outside [-1, 63]", what, start_state);
+    if (end_state < -1 || end_state > 63)
+        return fail("%s: end_state %d outside [-1, 63]", what, end_state);
+    const size_t m = poporon_amd_cc_symbols(cc, nbits), fb = nbits / 8 + (nbits % 8 != 0);
+    if (llr_stride < m)
+        return fail("%s: llr_stride %zu < the %zu symbols of a frame", what, llr_stride, m);
+    if (bits_stride < fb)
+        return fail("%s: bits_stride %zu < the %zu bytes of a frame", what, bits_stride, fb);
+    if (count == 0)
+        return true;
+    if (!d_llr || !d_bits)
+        return fail("%s: NULL argument", what);
+    const uint64_t blocks = poporon_amd_cc_blocks(cc, nbits), total = blocks * count;
+    for (uint64_t first = 0; first < total; first += cc->chunk)
+        HIP_OK(cck_decode(&cc->p, d_llr, llr_stride, nbits, blocks, first,
+                          (uint32_t)std::min<uint64_t>(cc->chunk, total - first), start_state, end_state, d_bits,
+                          bits_stride, d_metric, static_cast<hipStream_t>(stream)));
+    return true;
 }
 
 /* ------------------------------------------------------------------------ */
