@@ -1,16 +1,21 @@
 """Reed-Solomon rows built from chosen syndromes, and batch layouts with chosen waves.
 
-A helper module of the tests (not a conftest, no fixtures).  It does no field
-arithmetic of its own: everything comes from the CPU oracle (oracle/rs_oracle.c)
-and from linear algebra over GF(2) on what the oracle answers.
+A helper module of the tests (not a conftest, no fixtures).  No expected value comes
+from field arithmetic of its own: everything comes from the CPU oracle
+(oracle/rs_oracle.c) and from linear algebra over GF(2) on what the oracle answers.
+The one exception is bm_trace, a Berlekamp-Massey replay on the oracle's tables that
+only tags rows (which iteration the general kernels' narrow run stops at, the final L)
+and is itself checked against the oracle (trace_conditions).
 
-The map from the nr parity bytes of a row to its nr syndrome values is
-GF(2)-linear, and invertible whenever the code's roots are distinct.
-SyndromeMap reads its 8 nr x 8 nr bit matrix off the oracle's syndromes of the
-8 nr one-bit parity perturbations of the all-zero row, inverts it, and so turns
-any wanted syndrome vector S into the row [base | encode(base) ^ parity_for(S)].
-The same idea on a set of byte positions gives error patterns whose first k
-syndromes vanish (SyndromeMap.vanishing).
+Symbols have m <= 8 bits, one per byte, nn = 2^m - 1 (m = 8, nn = 255 for the split and
+errata suites).  The map from the nr parity symbols of a row to its nr syndrome values
+is GF(2)-linear on the low m bits of each symbol, and invertible whenever the code's
+roots are distinct.  SyndromeMap reads its m nr x m nr bit matrix off the oracle's
+syndromes of the m nr one-bit parity perturbations of the all-zero row, inverts it, and
+so turns any wanted syndrome vector S into the row [base | encode(base) ^ parity_for(S)].
+The same idea on a set of symbol positions gives error patterns whose first k
+syndromes vanish (SyndromeMap.vanishing).  Base messages are raw bytes: the codec masks
+them to m bits.
 
 The families below are rows that random error patterns produce once in 256
 steps of Berlekamp-Massey or never: runs of zero discrepancies, a late jump of
@@ -22,6 +27,10 @@ one lane.  Everything is seeded; every row stands on a random base message.
 The errata_* families further down are rows with erasure lists (a row of nr slot bytes,
 a count, stale bytes after it) for the errata kernels, with their own conditions
 (errata_conditions) and layouts (uniform_ne, lone_ne, degree_brackets, bp_mixes).
+
+The last section serves the general kernels (rs_generic.hip), which run a codeword on
+GL = 4 .. 64 lanes: the handoff family, general_pool / general_errata_pool (the
+families above thinned for long codes), group_layout and pair_layout.
 """
 import numpy as np
 
@@ -70,13 +79,21 @@ def gf2_left_null_space(m):
     return np.ascontiguousarray(a[rank:, k:])
 
 
-def _bits(b):
-    """(count, n) bytes -> (count, 8 n) bits"""
-    return np.unpackbits(np.ascontiguousarray(b, dtype=np.uint8), axis=1)
+def _bits(b, m=8):
+    """(count, n) symbols -> (count, m n) bits: the low m bits of each, the highest first"""
+    b = np.ascontiguousarray(b, dtype=np.uint8)
+    x = np.unpackbits(b, axis=1)
+    return x if m == 8 else np.ascontiguousarray(x.reshape(len(b), -1, 8)[:, :, 8 - m:]).reshape(len(b), -1)
 
 
-def _bytes(x):
-    return np.packbits(x.astype(np.uint8), axis=1)
+def _bytes(x, m=8):
+    """(count, m n) bits -> (count, n) symbols of m bits"""
+    x = x.astype(np.uint8)
+    if m == 8:
+        return np.packbits(x, axis=1)
+    sym = np.zeros((len(x), x.shape[1] // m, 8), np.uint8)
+    sym[:, :, 8 - m:] = x.reshape(len(x), -1, m)
+    return np.packbits(sym.reshape(len(x), -1), axis=1)
 
 
 def _mul(x, m):
@@ -148,14 +165,15 @@ class SyndromeMap:
 
     def __init__(self, oracle, size):
         self.o, self.size, self.nr = oracle, size, oracle.nroots
-        assert oracle.m == 8, "byte symbols"
+        self.m, self.nn = oracle.m, oracle.nn  # bits per symbol, 2^m - 1
+        assert 2 <= self.m <= 8, "symbols of at most a byte"
         self.t = self.nr // 2
         self.width = size + self.nr
         self.pad = oracle.nn - self.nr - size  # the zero symbols a shortened row stands for
         self.alog = oracle.tables()[0]
-        nb = 8 * self.nr
-        par = _bytes(np.eye(nb, dtype=np.uint8))  # the 8 nr one-bit parity perturbations
-        self.matrix = _bits(self.syndromes(np.zeros((nb, size), np.uint8), par))  # parity bits -> syndrome bits
+        nb = self.m * self.nr
+        par = _bytes(np.eye(nb, dtype=np.uint8), self.m)  # the m nr one-bit parity perturbations
+        self.matrix = _bits(self.syndromes(np.zeros((nb, size), np.uint8), par), self.m)  # parity bits -> syndrome bits
         self.inverse = gf2_inverse(self.matrix)
 
     # -- syndromes as values (the oracle gives logs) --
@@ -167,19 +185,19 @@ class SyndromeMap:
     def parity_for(self, S):
         """(count, nr) parity deltas whose syndromes (on zero data) are the value vectors S"""
         S = np.atleast_2d(np.asarray(S, dtype=np.uint8))
-        return _bytes(_mul(_bits(S), self.inverse))
+        return _bytes(_mul(_bits(S, self.m), self.inverse), self.m)
 
     def vanishing(self, positions, k):
         """Basis of the GF(2) null space of "values at these byte positions -> S_0 .. S_(k-1)":
-        (8 (w - k), 8 w) bits, w = len(positions); byte i of a member goes to positions[i]."""
-        w = len(positions)
-        unit = _bytes(np.eye(8 * w, dtype=np.uint8))
-        rows = np.zeros((8 * w, self.width), np.uint8)
+        (m (w - k), m w) bits, w = len(positions); symbol i of a member goes to positions[i]."""
+        w, m = len(positions), self.m
+        unit = _bytes(np.eye(m * w, dtype=np.uint8), m)
+        rows = np.zeros((m * w, self.width), np.uint8)
         for i, p in enumerate(positions):
             rows[:, p] = unit[:, i]
         syn = self.syndromes(rows[:, :self.size], rows[:, self.size:])
-        basis = gf2_left_null_space(_bits(syn[:, :k]))
-        assert basis.shape == (8 * max(w - k, 0), 8 * w), (basis.shape, w, k)
+        basis = gf2_left_null_space(_bits(syn[:, :k], m))
+        assert basis.shape == (m * max(w - k, 0), m * w), (basis.shape, w, k)
         return basis
 
     def vanishing_pattern(self, rng, positions, k):
@@ -187,14 +205,14 @@ class SyndromeMap:
         whose first k syndromes are zero (w >= k + 1)."""
         basis = self.vanishing(positions, k)
         for _ in range(1000):
-            v = _bytes(_mul(rng.integers(0, 2, (1, basis.shape[0])), basis))[0]
+            v = _bytes(_mul(rng.integers(0, 2, (1, basis.shape[0])), basis), self.m)[0]
             if v.all():
                 return v
         raise AssertionError("no full-weight pattern found")
 
     # -- rows --
     def base_rows(self, rng, n):
-        data = rng.integers(0, 256, (n, self.size), dtype=np.uint8)
+        data = rng.integers(0, 256, (n, self.size), dtype=np.uint8)  # raw bytes: the codec masks to m bits
         return np.concatenate([data, self.o.encode_batch(data)], 1)
 
     def _split(self, rows, tags, clean):
@@ -215,15 +233,15 @@ class SyndromeMap:
         """e random nonzero values at random positions of row c outside `avoid`"""
         free = np.setdiff1d(np.arange(self.width), np.asarray(avoid, dtype=np.int64))
         pos = rng.permutation(free)[:e]
-        rows[c, pos] ^= rng.integers(1, 256, pos.size, dtype=np.uint8)
+        rows[c, pos] ^= rng.integers(1, self.nn + 1, pos.size, dtype=np.uint8)
         return tuple(int(p) for p in pos)
 
     # -- the order of the reference's root search --
     def visit(self, pos):
         """When the reference's root search meets byte position pos of the row: it tries
-        the points i = 1 .. 255 in turn, and point i stands for location (i iprim - 1) mod
-        255, so location k = pos + pad is met at i = (k + 1) prim mod 255 (0 read as 255).
-        Returned as i - 1, 0 .. 254.  Integer arithmetic on exponents, no field arithmetic;
+        the points i = 1 .. nn in turn, and point i stands for location (i iprim - 1) mod
+        nn, so location k = pos + pad is met at i = (k + 1) prim mod nn (0 read as nn; nn = 255
+        for byte symbols).  Returned as i - 1, 0 .. nn - 1.  Integer arithmetic on exponents, no field arithmetic;
         last_visited() and every family row that promises its clean row back check it
         against the oracle.  Magnitude n, in this order, goes to list slot n: a list
         restores the row only when it names the damaged positions in this order."""
@@ -237,7 +255,7 @@ class SyndromeMap:
         return pos[np.argsort(self.visit(pos), kind="stable")]
 
     def last_visited(self):
-        """The position whose root the reference tries last (its point i = 255), found from
+        """The position whose root the reference tries last (its point i = nn), found from
         the oracle by trying each: on the zero codeword with two unlike errors at p and q,
         the erasure mode with count 0 hands magnitude 0 to slot 0 and magnitude 1 to slot 1
         (quirk Q3), so the list [q, p] restores the row exactly when q is met before p."""
@@ -277,18 +295,22 @@ def ordinary(sm, e, n, seed=0):
     rows = clean.copy()
     e_row = min(e, sm.width)
     pos = rng.permuted(np.tile(np.arange(sm.width), (n, 1)), axis=1)[:, :e_row]
-    val = rng.integers(1, 256, (n, e_row), dtype=np.uint8)
+    val = rng.integers(1, sm.nn + 1, (n, e_row), dtype=np.uint8)
     np.put_along_axis(rows, pos, np.take_along_axis(rows, pos, 1) ^ val, 1)
     return sm._split(rows, [Tag("ordinary", tuple(int(p) for p in pos[c]), e=e) for c in range(n)], clean)
 
 
-def zero_run(sm, draws=1, seed=0):
-    """For every k in 1 .. t-1 and w in k+1 .. t: a vanishing pattern of weight w and a
+def zero_run(sm, draws=1, seed=0, ks=None):
+    """For every k in 1 .. t-1 (or in `ks`: long codes) and w in k+1 .. t: a vanishing pattern
+    of weight w and a
     ordinary errors elsewhere, a <= min(t - w, k // 2).  Correctable; Berlekamp-Massey
     sees k - 2a zero discrepancies in a row and then lengthens by more than one."""
     rng = _rng(sm, seed, "zero_run")
     t = sm.t
-    combos = [(k, w) for k in range(1, t) for w in range(k + 1, t + 1) if w <= sm.width] * draws
+    combos = [(k, w) for k in range(1, t) for w in range(k + 1, t + 1) if w <= sm.width]
+    if ks is not None:  # (w: the least, the greatest and one between)
+        combos = [(k, w) for k, w in combos if k in ks and w in (k + 1, (k + 1 + t) // 2, t)]
+    combos = combos * draws
     clean = sm.base_rows(rng, len(combos))
     rows = clean.copy()
     tags = []
@@ -301,12 +323,12 @@ def zero_run(sm, draws=1, seed=0):
     return sm._split(rows, tags, clean)
 
 
-def late_discrepancy(sm, draws=3, seed=0):
-    """e ordinary errors, e in 0 .. t, then a nonzero value XORed into one syndrome S_j,
-    for every j: L jumps to j + 1 - e late, with B shifted many times."""
+def late_discrepancy(sm, draws=3, seed=0, es=None, js=None):
+    """e ordinary errors, e in 0 .. t (or in `es`), then a nonzero value XORed into one syndrome
+    S_j, for every j (or those in `js`): L jumps to j + 1 - e late, with B shifted many times."""
     rng = _rng(sm, seed, "late_discrepancy")
     t, nr = sm.t, sm.nr
-    combos = [(e, j) for e in range(t + 1) for j in range(nr)] * draws
+    combos = [(e, j) for e in (range(t + 1) if es is None else es) for j in (range(nr) if js is None else js)] * draws
     n = len(combos)
     clean = sm.base_rows(rng, n)
     rows = clean.copy()
@@ -314,24 +336,25 @@ def late_discrepancy(sm, draws=3, seed=0):
     tags = []
     for c, (e, j) in enumerate(combos):
         pos = sm._scatter(rng, rows, c, min(e, sm.width))
-        S[c, j] = rng.integers(1, 256)
+        S[c, j] = rng.integers(1, sm.nn + 1)
         tags.append(Tag("late_discrepancy", pos, e=e, j=j))
     rows[:, sm.size:] ^= sm.parity_for(S)
     return sm._split(rows, tags, clean)
 
 
-def sparse(sm, values=4, pairs=48, seed=0):
+def sparse(sm, values=4, pairs=48, seed=0, js=None):
     """Exactly one nonzero syndrome S_j for every j (`values` values each), and exactly
     two for a seeded set of pairs.  A single S_j = d with j >= t leaves the locator
     1 + d' x^(j+1): j = t - 1 gives 1 + d' x^t, and where j + 1 divides 255 (17 for 32
     roots, 15 for 16, 5 for 8) the locator has j + 1 > t roots for one d in j + 1; the
-    reference then "corrects" j + 1 symbols of a full-length row.  Those j get every d."""
+    reference then "corrects" j + 1 symbols of a full-length row.  Those j get every d.
+    (255: nn = 2^m - 1 for symbols of m bits.  js: the singles' j, for long codes.)"""
     rng = _rng(sm, seed, "sparse")
     nr = sm.nr
     S, tags = [], []
-    for j in range(nr):
-        every = j + 1 > sm.t and 255 % (j + 1) == 0
-        for v in rng.permutation(np.arange(1, 256))[:255 if every else values]:
+    for j in (range(nr) if js is None else js):
+        every = j + 1 > sm.t and sm.nn % (j + 1) == 0
+        for v in rng.permutation(np.arange(1, sm.nn + 1))[:sm.nn if every else values]:
             s = np.zeros(nr, np.uint8)
             s[j] = v
             S.append(s)
@@ -339,14 +362,14 @@ def sparse(sm, values=4, pairs=48, seed=0):
     for _ in range(pairs):
         i, j = sorted(int(x) for x in rng.permutation(nr)[:2])
         s = np.zeros(nr, np.uint8)
-        s[i], s[j] = rng.integers(1, 256, 2)
+        s[i], s[j] = rng.integers(1, sm.nn + 1, 2)
         S.append(s)
         tags.append(Tag("sparse", None, i=i, j=j))
     rows, clean = sm.rows_for(rng, np.array(S))
     return sm._split(rows, tags, clean)
 
 
-def padding_roots(sm, full, seed=0):
+def padding_roots(sm, full, seed=0, es=None):
     """Shortened sizes: the syndromes of e errors, e in 1 .. t, on the full-length code
     (`full`: the SyndromeMap of size k), 1 .. e of them inside the padding, transplanted
     onto the short row.  The locator is valid and all its roots are found, but a location
@@ -355,11 +378,13 @@ def padding_roots(sm, full, seed=0):
     pad = full.size - sm.size
     assert pad > 0 and full.nr == sm.nr
     combos = [(e, p) for e in range(1, sm.t + 1) for p in range(1, e + 1) if p <= pad and e - p <= sm.width]
+    if es is not None:  # long codes: these e, with one, half and all of the errors inside the padding
+        combos = [(e, p) for e, p in combos if e in es and p in (1, (e + 1) // 2, min(e, pad))]
     err = np.zeros((len(combos), full.width), np.uint8)
     tags = []
     for c, (e, p) in enumerate(combos):
         pos = np.concatenate([rng.permutation(pad)[:p], pad + rng.permutation(sm.width)[:e - p]])
-        err[c, pos] = rng.integers(1, 256, e, dtype=np.uint8)
+        err[c, pos] = rng.integers(1, sm.nn + 1, e, dtype=np.uint8)
         tags.append(Tag("padding_roots", None, e=e, inside=p))
     S = full.syndromes(err[:, :full.size], err[:, full.size:])
     rows, clean = sm.rows_for(rng, S)
@@ -374,10 +399,10 @@ def positions(sm, seed=0):
     rows = clean.copy()
     tags = []
     for p in range(W):
-        rows[p, p] ^= rng.integers(1, 256)
+        rows[p, p] ^= rng.integers(1, sm.nn + 1)
         tags.append(Tag("positions", (p,), at=p, run=1))
     for s in range(W - t + 1):
-        rows[W + s, s:s + t] ^= rng.integers(1, 256, t, dtype=np.uint8)
+        rows[W + s, s:s + t] ^= rng.integers(1, sm.nn + 1, t, dtype=np.uint8)
         tags.append(Tag("positions", tuple(range(s, s + t)), at=s, run=t))
     return sm._split(rows, tags, clean)
 
@@ -394,20 +419,35 @@ def family_pool(sm, full=None, zero_run_draws=1, late_draws=3, seed=0):
 # ---------------------------------------------------------------------------
 # conditions on the oracle's results alone: no family may quietly become trivial
 # ---------------------------------------------------------------------------
-def family_conditions(pool, want, relaxed=()):
-    """pool: rows and tags; want: Oracle.decode_batch of them.  `relaxed` names the
+def _all_refused(pool, want):
+    """The condition "all_refused" of a code whose exponents pass 2^16: the reference's own
+    check of a correction (its 16-bit exponent arithmetic) refuses every dirty row, with
+    corrected_num counted where a locator was found, and passes every clean one."""
+    ok, cor = want[0], want[1]
+    dirty = (np.concatenate([pool.data, pool.parity], 1) != pool.clean).any(1)
+    assert dirty.any() and not ok[dirty].any() and ok[~dirty].all(), "all_refused: a dirty row succeeds"
+    assert (cor[dirty] > 0).any() and (cor[dirty] == 0).any()
+    return {"all_refused": (int(dirty.sum()), int((cor[dirty] > 0).sum()))}
+
+
+def family_conditions(pool, want, relaxed=(), nn=255):
+    """pool: rows and tags; want: Oracle.decode_batch of them; nn: the field's 2^m - 1 (255 in
+    the text below).  `relaxed` names the
     conditions a code is excused from (see the codes' entries in the tests):
       "late_fails"     no late_discrepancy row with e > 0 succeeds (e = 0 is a sparse single)
       "late_counted"   at least one late_discrepancy failure has corrected_num > 0
       "sparse_zero"    a sparse single S_j fails with corrected_num == 0, or j + 1 > t divides
                        255 and it succeeds with corrected_num == j + 1 (see sparse())
       "padding_fails"  padding_roots rows fail with corrected_num == 0
+      "all_refused"    instead of all the above: see _all_refused
     Returns the counts it looked at, for the record."""
     ok, cor, od, op = want
     fam = pool.families()
     failed = ok == 0
     assert (od[failed] == pool.data[failed]).all() and (op[failed] == pool.parity[failed]).all(), \
         "a failed row was modified"
+    if "all_refused" in relaxed:
+        return _all_refused(pool, want)
     seen = {}
     size = pool.data.shape[1]
     tt = pool.parity.shape[1] // 2
@@ -439,7 +479,7 @@ def family_conditions(pool, want, relaxed=()):
                        for t in pool.tags])
     if single.any():
         j1 = np.array([t.j + 1 if s else 0 for t, s in zip(pool.tags, single)])
-        full = single & (ok == 1) & (cor == j1) & (j1 > tt) & (255 % np.maximum(j1, 1) == 0)
+        full = single & (ok == 1) & (cor == j1) & (j1 > tt) & (nn % np.maximum(j1, 1) == 0)
         if "sparse_zero" not in relaxed:
             assert ((failed & (cor == 0)) | full)[single].all(), "sparse singles: a row succeeds or counts"
         seen["sparse"] = (int(single.sum()), int(ok[single].sum()), int((cor[single] > 0).sum()))
@@ -494,7 +534,7 @@ class _Listed:
 
     def damage(self, c, pos):
         pos = np.asarray(pos, dtype=np.int64)
-        self.rows[c, pos] ^= self.rng.integers(1, 256, pos.size, dtype=np.uint8)
+        self.rows[c, pos] ^= self.rng.integers(1, self.sm.nn + 1, pos.size, dtype=np.uint8)
 
     def same_row(self, c, src):
         """row c: the clean row, the damage and the junk of row src"""
@@ -615,7 +655,7 @@ def errata_late(sm, draws=1, seed=0):
         e = int(rng.integers(0, min((nr - ne) // 2, W - ne) + 1))
         pos = rng.permutation(W)[:ne + e]
         b.damage(c, pos)
-        S[c, j] = rng.integers(1, 256)
+        S[c, j] = rng.integers(1, sm.nn + 1)
         b.add(_ordered(pos[:ne], ORDERS[c % 3]), positions=pos, ne=ne, e=e, j=j)
     b.rows[:, sm.size:] ^= sm.parity_for(S)
     return b.done()
@@ -631,7 +671,7 @@ def errata_sparse(sm, seed=0):
     b = _Listed(sm, rng, "errata_sparse", len(combos))
     S = np.zeros((len(combos), nr), np.uint8)
     for c, (j, ne, asc) in enumerate(combos):
-        S[c, j] = rng.integers(1, 256)
+        S[c, j] = rng.integers(1, sm.nn + 1)
         listed = rng.permutation(W)[:ne]
         if not asc and ne >= 2 and (np.diff(listed) > 0).all():
             listed = listed[::-1]
@@ -704,20 +744,21 @@ def errata_padding(sm, full, seed=0):
         short = rng.permutation(W)
         era, inside = short[:ne], short[ne:ne + e - p]
         at = np.concatenate([rng.permutation(pad)[:p], pad + inside])
-        err[c, at] = rng.integers(1, 256, e, dtype=np.uint8)
+        err[c, at] = rng.integers(1, sm.nn + 1, e, dtype=np.uint8)
         b.damage(c, era)
         b.add(_ordered(era, ORDERS[c % 3]), positions=tuple(era) + tuple(inside), ne=ne, e=e, inside=p)
     b.rows[:, sm.size:] ^= sm.parity_for(full.syndromes(err[:, :full.size], err[:, full.size:]))
     return b.done()
 
 
-def errata_outside(sm, seed=0):
+def errata_outside(sm, seed=0, ne_range=None):
     """A slot past the codeword, size + nr or 255, in threes on one damaged row (ne erasures
     and e errors, ne + e < nr): the plain list; the list with that slot counted besides;
     the plain list with that value in the last stale slot, which no magnitude reaches."""
     rng = _rng(sm, seed, "errata_outside")
     nr, W = sm.nr, sm.width
-    spec = [(ne, out) for ne in _ne_range(sm, range(nr)) for out in sorted({W, 255})]
+    spec = [(ne, out) for ne in _ne_range(sm, range(nr) if ne_range is None else [n for n in ne_range if n < nr])
+            for out in sorted({W, 255})]
     b = _Listed(sm, rng, "errata_outside", 3 * len(spec))
     for i, (ne, out) in enumerate(spec):
         e = int(rng.integers(0, min((nr - 1 - ne) // 2, W - ne) + 1))
@@ -733,12 +774,12 @@ def errata_outside(sm, seed=0):
     return b.done()
 
 
-def errata_repeats(sm, seed=0):
+def errata_repeats(sm, seed=0, ne_range=None):
     """A slot counted twice, next to itself and apart; a counted slot repeated in the first
     stale slot; nr slots ascending but for one pair of equal neighbours, at every index."""
     rng = _rng(sm, seed, "errata_repeats")
     nr, W = sm.nr, sm.width
-    spec = [(kind, ne, 0) for ne in _ne_range(sm, None, 2) for kind in ("adjacent", "apart", "stale")
+    spec = [(kind, ne, 0) for ne in _ne_range(sm, ne_range, 2) for kind in ("adjacent", "apart", "stale")
             if (kind != "apart" or ne >= 3) and (kind != "stale" or ne < nr)]
     spec += [("asc_pair", nr, i) for i in range(nr - 1) if nr <= W]
     b = _Listed(sm, rng, "errata_repeats", len(spec))
@@ -764,11 +805,11 @@ def errata_repeats(sm, seed=0):
     return b.done()
 
 
-def count_zero(sm, full=None, seed=0):
-    """The rows of the errors-only family_pool under the erasure mode with count 0 and junk
-    in the stale slots (quirk Q3: the magnitudes go to the stale slots)."""
+def count_zero(sm, full=None, seed=0, src=None):
+    """The rows of the errors-only family_pool (or of the pool `src`) under the erasure mode
+    with count 0 and junk in the stale slots (quirk Q3: the magnitudes go to the stale slots)."""
     rng = _rng(sm, seed, "count_zero")
-    src = family_pool(sm, full, seed=seed)
+    src = family_pool(sm, full, seed=seed) if src is None else src
     tags = []
     slots = rng.integers(0, 256, (len(src), sm.nr), dtype=np.uint8)
     for c, t in enumerate(src.tags):
@@ -823,6 +864,7 @@ def errata_conditions(pool, want, sm, relaxed=()):
       errata_padding    failure with corrected_num == 0 ("padding_fails" excuses a code)
       errata_outside    the row with the outside value in its last stale slot gives what the
                         plain row gives
+    ("all_refused" in `relaxed`: _all_refused instead of all these.)
     Returns the counts it looked at, for the record."""
     ok, cor, od, op = want
     fam = pool.families()
@@ -831,6 +873,8 @@ def errata_conditions(pool, want, sm, relaxed=()):
     failed = ok == 0
     assert (od[failed] == pool.data[failed]).all() and (op[failed] == pool.parity[failed]).all(), \
         "a failed row was modified"
+    if "all_refused" in relaxed:
+        return _all_refused(pool, want)
     restored = (od == pool.clean[:, :size]).all(1) & (op == pool.clean[:, size:]).all(1)
     untouched = (od == pool.data).all(1) & (op == pool.parity).all(1)
     damaged = (np.concatenate([pool.data, pool.parity], 1) != pool.clean).sum(1)
@@ -1086,3 +1130,447 @@ def bp_mixes(pool, want, waves=4):
     clean[WAVE + 5] = k["clean"][0]
     mix[1::2] = _fill(k["pending"], n // 2)
     return {"solved": solved, "pending_last": last, "one_clean": clean, "mix": mix}
+
+
+# ---------------------------------------------------------------------------
+# the general kernels (rs_generic.hip): a codeword on GL lanes
+#
+# rsgw_decode_k<., GL> keeps index i = lane + GL q of the locator in register slot q, nq =
+# (nr + GL) // GL slots.  With nq >= 2 Berlekamp-Massey starts narrow, on NQ = 1 (nq = 2) or
+# 2 (nq >= 3) slots, and stops before the first iteration r at which B holds a nonzero at
+# index GL NQ - 1 (gw_top_set); a run on all slots goes on from r: the hand-off.
+# ---------------------------------------------------------------------------
+GW_GROUP_MIN = 256  # rs_generic.hip: a batch below it runs every code on 64 lanes per codeword
+GW_WORKGROUP = 256  # lanes of one rsgw_decode_k workgroup
+
+
+def group_lanes(nn, count=GW_GROUP_MIN):
+    """GL of a decode batch (rsgw_decode_launch)"""
+    if count < GW_GROUP_MIN:
+        return 64
+    return 4 if nn <= 15 else 8 if nn <= 31 else 16 if nn <= 63 else 32 if nn <= 127 else 64
+
+
+def narrow_top(nr, gl):
+    """The index GL NQ - 1 of B that ends the narrow run, None where nq = 1 (no narrow run)."""
+    nq = (nr + gl) // gl
+    return None if nq < 2 else gl * (1 if nq == 2 else 2) - 1
+
+
+def _spread(lo, hi, n, also=()):
+    """About n integers across lo .. hi, both ends among them, and those of `also` in range"""
+    if hi < lo:
+        return []
+    return sorted({int(x) for x in np.linspace(lo, hi, min(n, hi - lo + 1))} | {int(x) for x in also if lo <= x <= hi})
+
+
+def bm_trace(sm, S, tops=()):
+    """Berlekamp-Massey (errors only) on the syndrome values S (count, nr), on the oracle's log
+    and antilog tables, all rows at once.  FOR TAGS AND COVERAGE CONDITIONS ONLY: no expected
+    value of any test comes from here, and trace_conditions checks it against the oracle.
+    Returns the final L (count,) and, for each T of `tops`, the first iteration r (1 .. nr) at
+    whose start B[T] != 0, 0 where there is none or the row is clean (no BM runs on it)."""
+    alog, log, _ = sm.o.tables()
+    alog, log = alog.astype(np.int64), log.astype(np.int64)
+    nn = sm.nn
+    S = np.atleast_2d(np.asarray(S)).astype(np.int64)
+    n, nr = S.shape
+
+    def mul(a, b):
+        return np.where((a == 0) | (b == 0), 0, alog[(log[a] + log[b]) % nn])
+
+    lam = np.zeros((n, nr + 2), np.int64)
+    lam[:, 0] = 1
+    B, L = lam.copy(), np.zeros(n, np.int64)
+    first = {T: np.zeros(n, np.int64) for T in tops}
+    dirty = S.any(1)
+    for r in range(1, nr + 1):
+        for T in tops:
+            first[T][(first[T] == 0) & (B[:, T] != 0) & dirty] = r
+        disc = np.bitwise_xor.reduce(mul(lam[:, :r], S[:, r - 1::-1]), axis=1)  # sum of Lambda_i S_(r-1-i)
+        Bm = np.zeros_like(B)
+        Bm[:, 1:] = B[:, :-1]
+        lengthen = (disc != 0) & (2 * L <= r - 1)
+        inv = np.where(disc != 0, alog[(nn - log[disc]) % nn], 0)
+        B = np.where(lengthen[:, None], mul(lam, inv[:, None]), Bm)
+        lam = lam ^ mul(disc[:, None], Bm)
+        L = np.where(lengthen, r - L, L)
+    return L, first
+
+
+def tag_trace(sm, pool, gls):
+    """bm_trace of every row of an errors-only pool: each tag gets L (the final length) and
+    handoff, {GL: the iteration at which the narrow run of that GL stops, 0 for none}."""
+    assert not pool.counts.any()
+    tops = sorted({narrow_top(sm.nr, gl) for gl in gls} - {None})
+    L, first = bm_trace(sm, sm.syndromes(pool.data, pool.parity), tops)
+    for c, g in enumerate(pool.tags):
+        g.params["L"] = int(L[c])
+        g.params["handoff"] = {gl: int(first[narrow_top(sm.nr, gl)][c]) if narrow_top(sm.nr, gl) is not None else 0
+                               for gl in gls}
+    return L
+
+
+def trace_conditions(pool, want):
+    """The trace against the oracle: on every row that the oracle corrects, the final L is its
+    corrected_num (a clean row: both 0)."""
+    ok, cor = want[0], want[1]
+    L = np.array([g.L for g in pool.tags])
+    bad = (ok == 1) & (L != cor)
+    assert not bad.any(), f"bm_trace: L {L[bad][:5]} != corrected_num {cor[bad][:5]} at rows {np.nonzero(bad)[0][:5]}"
+    return int((ok == 1).sum())
+
+
+def handoff(sm, gl, per_r=6, seed=0):
+    """Rows whose narrow run on GL = gl lanes stops at a chosen iteration r, for the earliest r
+    (GL NQ: the first GL NQ - 1 syndromes zero, the next nonzero), the last (nr) and up to six
+    between.  Candidates: e errors, e = 1 .. min(t, nr - GL NQ), whose B climbs one index an
+    iteration once L has settled and reaches the top at r = GL NQ + e (they succeed); the same
+    with a value XORed into one syndrome S_j, j >= r - 1, which the run on all slots meets
+    after the hand-off (they fail, or are miscorrected); GL NQ - 1 zero syndromes, a nonzero one
+    and random ones after it (the earliest r; they fail).  bm_trace says at which r each
+    candidate stops, and nothing else; per_r rows are kept for each chosen r, half of them of
+    the first kind where there are any."""
+    T = narrow_top(sm.nr, gl)
+    assert T is not None, "nq = 1: no narrow run"
+    rng = _rng(sm, seed + gl, "handoff")
+    nr, t, W = sm.nr, sm.t, sm.width
+    es = [e for e in range(1, min(t, nr - T - 1, W) + 1)]
+    spec = [("errors", e, None) for e in es] * 3
+    spec += [("late", e, int(rng.integers(T + e, nr))) for e in [0] + es for _ in range(3)]
+    spec += [("zeros", 0, None)] * 6
+    n = len(spec)
+    clean = sm.base_rows(rng, n)
+    rows = clean.copy()
+    S = np.zeros((n, nr), np.uint8)
+    tags = []
+    for c, (kind, e, j) in enumerate(spec):
+        pos = sm._scatter(rng, rows, c, e)
+        if kind == "late":
+            S[c, j] = rng.integers(1, sm.nn + 1)
+        elif kind == "zeros":
+            S[c, T:] = rng.integers(1, sm.nn + 1, nr - T)
+        tags.append(Tag("handoff", pos if kind != "zeros" else None, gl=gl, kind=kind, e=e, j=j))
+    rows[:, sm.size:] ^= sm.parity_for(S)
+    r = bm_trace(sm, sm.syndromes(rows[:, :sm.size], rows[:, sm.size:]), (T,))[1][T]
+    found = sorted(set(r[r > 0].tolist()))
+    assert found and found[0] >= T + 1, (found, T)
+    chosen = [found[i] for i in _spread(0, len(found) - 1, 8)]
+    keep = []
+    for rr in chosen:
+        at = np.nonzero(r == rr)[0]
+        good = [c for c in at if spec[c][0] == "errors"][:per_r // 2]
+        keep += good + [c for c in at if spec[c][0] != "errors"][:per_r - len(good)]
+    for c in keep:
+        tags[c].params["r"] = int(r[c])
+    keep = np.array(keep)
+    return sm._split(rows[keep], [tags[c] for c in keep], clean[keep])
+
+
+def take(pool, idx):
+    """The rows idx of a pool as a pool"""
+    return Pool(pool.data[idx], pool.parity[idx], [pool.tags[i] for i in idx], pool.slots[idx], pool.counts[idx])
+
+
+def general_pool(sm, full=None, gls=(64,), seed=0):
+    """The errors-only families for a code of the general kernels, thinned where t > 8 (a long
+    code has thousands of (k, w) and (e, j) cells): the parameters are spread over their range,
+    both ends and the indices around every narrow top GL NQ - 1 among them; the handoff family
+    for every GL of `gls` that has a narrow run; ordinary rows of 0 .. t + 1 errors.  Every
+    tag carries the trace's L and handoff (tag_trace)."""
+    nr, t = sm.nr, sm.t
+    tops = sorted({narrow_top(nr, gl) for gl in gls} - {None})
+    thin = t > 8
+    around = [T + d for T in tops for d in (-1, 0, 1)]
+    es = _spread(0, t, 6) if thin else None
+    # (the singles S_j that a full-length row "corrects" in j + 1 > t places, see sparse(): past a narrow
+    # top they are the rows whose success rests on the run after the hand-off)
+    deep = [j for j in range(t, nr) if sm.nn % (j + 1) == 0]
+    js = _spread(0, nr - 1, 8, around + deep + [t - 1, t]) if thin else None
+    parts = []
+    if t >= 2:
+        parts.append(zero_run(sm, 1, seed, ks=_spread(1, t - 1, 5) if thin else None))
+    parts += [late_discrepancy(sm, 1 if thin else 2, seed, es, js), sparse(sm, 2 if thin else 4, 16, seed, js),
+              positions(sm, seed)]
+    if full is not None and full.size > sm.size:
+        parts.append(padding_roots(sm, full, seed, es=_spread(1, t, 6) if thin else None))
+    done = set()
+    for gl in gls:
+        T = narrow_top(nr, gl)
+        if T is not None and T not in done:
+            done.add(T)
+            parts.append(handoff(sm, gl, seed=seed))
+    parts += [ordinary(sm, e, 6) for e in (_spread(0, t + 1, 8, (1, 2, t - 1, t)) if thin else range(t + 2))]
+    pool = Pool.concat(parts)
+    tag_trace(sm, pool, gls)
+    return pool
+
+
+def general_ne_range(sm, gls):
+    """The erasure counts around the narrow run's conditions ne < GL and ne < 2 GL for each GL,
+    0 .. 3, nr - 1 and nr, where the code and the row have them"""
+    want = {0, 1, 2, 3, sm.nr - 1, sm.nr} | {x for gl in gls for x in (gl - 1, gl, 2 * gl - 1, 2 * gl)}
+    return sorted(x for x in want if 0 <= x <= min(sm.nr, sm.width))
+
+
+def _locator(sm, listed):
+    """Coefficients (values, index 0 .. len(listed)) of the erasure locator prod (1 + X_l x), X_l =
+    alpha^(prim (nn - 1 - (position + pad))), on the oracle's tables.  Like bm_trace: for choosing
+    and tagging rows only."""
+    alog, log, _ = sm.o.tables()
+    nn = sm.nn
+    lam = [1] + [0] * len(listed)
+    for d, p in enumerate(listed):
+        x = (sm.o.prim * (nn - 1 - (int(p) + sm.pad))) % nn
+        for i in range(d + 1, 0, -1):
+            if lam[i - 1]:
+                lam[i] ^= int(alog[(int(log[lam[i - 1]]) + x) % nn])
+    return lam
+
+
+def errata_top_gap(sm, gls, draws=4, seed=0):
+    """Lists of ne = GL NQ - 1 erased positions, for each narrow top of `gls`, whose locator has a
+    zero at index ne - 1 and a nonzero at ne: the narrow run starts with B's top index set and the
+    one below it clear, and must hand over before its first iteration.  The last position is
+    solved for (the sum of the 1 / X_l vanishes).  Every erased symbol is damaged, with e = 1 ..
+    errors elsewhere (ne + 2 e <= nr), so the locator grows past the top."""
+    rng = _rng(sm, seed, "errata_top_gap")
+    alog, log, _ = sm.o.tables()
+    nn, nr, W = sm.nn, sm.nr, sm.width
+    iprim = pow(int(sm.o.prim), -1, nn)
+    spec = []
+    for T in sorted({narrow_top(nr, gl) for gl in gls} - {None}):
+        found = 0
+        for _ in range(4000):
+            if found == draws or T < 2 or T >= nr:
+                break
+            pos = [int(p) for p in rng.permutation(W)[:T - 1]]
+            v = 0
+            for p in pos:
+                v ^= int(alog[(-sm.o.prim * (nn - 1 - (p + sm.pad))) % nn])
+            if v == 0:
+                continue
+            last = (nn - 1 - (-int(log[v])) * iprim) % nn - sm.pad  # 1 / X_last = v
+            if not 0 <= last < W or last in pos:
+                continue
+            listed = pos + [last]
+            lam = _locator(sm, listed)
+            assert lam[T] != 0 and lam[T - 1] == 0, (T, lam[T - 1:])
+            e = 1 + found % max(1, min((nr - T) // 2, W - T))
+            if T + 2 * e <= nr and T + e <= W:
+                spec.append((T, listed, e))
+                found += 1
+    b = _Listed(sm, rng, "errata_top_gap", len(spec))
+    for c, (T, listed, e) in enumerate(spec):
+        b.damage(c, listed)
+        extra = sm._scatter(rng, b.rows, c, e, avoid=listed)
+        b.add(listed, positions=tuple(listed) + extra, ne=T, e=e, top=T)
+    return b.done()
+
+
+def general_errata_pool(sm, src, full=None, gls=(64,), seed=0):
+    """errata_grid, idle_erasures, errata_outside, errata_repeats at the counts of
+    general_ne_range, errata_top_gap, and count_zero of the rows `src` (an errors-only pool)"""
+    nes = general_ne_range(sm, gls)
+    parts = [errata_grid(sm, nes, seed=seed), idle_erasures(sm, nes, seed), errata_outside(sm, seed, nes),
+             errata_repeats(sm, seed, nes), errata_top_gap(sm, gls, seed=seed), count_zero(sm, full, seed, src=src)]
+    return Pool.concat([p for p in parts if len(p[2])])  # (errata_top_gap: none where no narrow top has room)
+
+
+GENERAL_ERRATA_FAMILIES = ("errata_grid", "idle_erasures", "errata_outside", "errata_repeats", "count_zero")
+
+
+def general_conditions(pool, want, sm, gls, excused=()):
+    """Coverage of an errors-only general_pool, on the oracle's results and the tags alone;
+    `excused` names what a code cannot meet (the tests give the reason with each):
+      every family is there (padding_roots on a shortened size, handoff where some GL has nq >= 2)
+      for each GL with nq >= 2: rows hand off at no fewer than 4 distinct r ("few_handoffs": the
+        code has fewer than 4 iterations GL NQ .. nr, and rows at each of them), the earliest
+        (GL NQ) and nr among them, and some of the rows that hand off succeed and some fail
+        ("handoff_all_fail": GL NQ = nr, so a row hands off only when its first nr - 1
+        syndromes vanish, and then L = nr > t)
+      a shortened size has a padding_roots row refused with corrected_num 0 ("padding_fails")
+    Returns what it saw, for the record."""
+    ok, cor = want[0], want[1]
+    fam = pool.families()
+    need = {"late_discrepancy", "sparse", "positions", "ordinary"} | ({"zero_run"} if sm.t >= 2 else set())
+    seen = {}
+    for gl in gls:
+        T = narrow_top(sm.nr, gl)
+        if T is None:
+            continue
+        need.add("handoff")
+        r = np.array([g.handoff[gl] for g in pool.tags])
+        rs = sorted(set(r[r > 0].tolist()))
+        assert rs and rs[0] == T + 1 and rs[-1] == sm.nr, (gl, rs)
+        assert len(rs) >= 4 or ("few_handoffs" in excused and len(rs) == sm.nr - T), (gl, rs)
+        if "handoff_all_fail" in excused:
+            assert rs == [sm.nr] and not ok[r > 0].any(), (gl, rs)
+        else:
+            assert ok[r > 0].any() and not ok[r > 0].all(), \
+                f"GL {gl}: the hand-off rows all {'succeed' if ok[r > 0].all() else 'fail'}"
+        seen[f"handoff GL {gl}"] = (len(rs), int((r > 0).sum()), int(ok[r > 0].sum()))
+    if sm.pad > 0:
+        need.add("padding_roots")
+        pr = fam == "padding_roots"
+        assert "padding_fails" in excused or ((ok[pr] == 0) & (cor[pr] == 0)).any(), "no root-in-padding refusal"
+    assert need <= set(fam), need - set(fam)
+    return seen
+
+
+def general_sizes(nn, nr):
+    """full length, a shortened size with padding, and 1"""
+    k = nn - nr
+    return sorted({k, max(2, k // 3), 1}, reverse=True)
+
+
+def general_case(o, size, full=None, excused=(), threads=8):
+    """What the tests of the general kernels share for one (code, size): the errors-only pool
+    with the oracle's decode and the rows' syndromes (log form), the pool of rows with lists
+    (count_zero on every third row of the first) with the oracle's decode, and every
+    condition on them (family_conditions, general_conditions, trace_conditions,
+    errata_conditions; `excused`: the names a code is excused from), checked here."""
+    from types import SimpleNamespace
+    k = o.nn - o.nroots
+    full = SyndromeMap(o, k) if full is None else full
+    sm = full if size == k else SyndromeMap(o, size)
+    gls = tuple(sorted({group_lanes(o.nn), 64}))
+    pool = general_pool(sm, full, gls)
+    want = o.decode_batch(pool.data, pool.parity, threads=threads)
+    seen = family_conditions(pool, want, excused, nn=o.nn)
+    seen.update(general_conditions(pool, want, sm, gls, excused))
+    seen["traced"] = trace_conditions(pool, want)
+    epool = general_errata_pool(sm, take(pool, np.arange(0, len(pool), 3)), full, gls)
+    ewant = decode_lists(o, epool, threads=threads)
+    eseen = errata_conditions(epool, ewant, sm, excused)
+    assert "all_refused" in excused or set(eseen) == set(GENERAL_ERRATA_FAMILIES), set(eseen)
+    # errata_top_gap: wherever a narrow top GL NQ - 1 leaves room for an error (GL NQ + 1 <= nr); corrected in full
+    gap = epool.families() == "errata_top_gap"
+    tops = {narrow_top(sm.nr, gl) for gl in gls} - {None}
+    assert {g.top for g in epool.tags if g.family == "errata_top_gap"} == {T for T in tops if 2 <= T and T + 2 <= sm.nr}
+    if "all_refused" not in excused:
+        assert (ewant[0][gap] == 1).all() and (ewant[1][gap] == [g.ne + g.e for g in epool.tags if g.family == "errata_top_gap"]).all()
+    eseen["errata_top_gap"] = int(gap.sum())
+    assert set(epool.families()) - {"errata_top_gap"} == set(GENERAL_ERRATA_FAMILIES)
+    syn = o.syndrome_batch(pool.data, pool.parity)[1]
+    for a in (pool.data, pool.parity, epool.data, epool.parity, epool.slots, epool.counts, syn) + tuple(want) + tuple(ewant):
+        a.setflags(write=False)
+    return SimpleNamespace(o=o, sm=sm, size=size, gls=gls, pool=pool, want=want, syn=syn, seen=seen, epool=epool,
+                           ewant=ewant, eseen=eseen)
+
+
+# -- layouts --
+def general_kinds(pool, want, gl):
+    """The rows of an errors-only general_pool by what rsgw_decode_k<., gl> makes of them, from
+    the tags and the oracle's results: name -> index array.  clean; e<n>: n ordinary errors
+    (up to eight n, 1 and t among them); fail: dirty rows the oracle refuses that do
+    not hand off; handoff<r>: rows whose narrow run stops at r (the earliest, the last and one
+    between); handoff_fail: refused rows that hand off."""
+    ok = want[0]
+    t = pool.parity.shape[1] // 2
+    e_of = np.array([g.e if g.family == "ordinary" else -1 for g in pool.tags])
+    r = np.array([g.handoff.get(gl, 0) for g in pool.tags])
+    kinds = {"clean": np.nonzero(e_of == 0)[0]}
+    have = sorted(set(e_of[(e_of >= 1) & (e_of <= t)].tolist()))
+    for e in [have[i] for i in _spread(0, len(have) - 1, 8)]:
+        kinds[f"e{e}"] = np.nonzero(e_of == e)[0]
+    dirty = (pool.data != pool.clean[:, :pool.data.shape[1]]).any(1) | (pool.parity != pool.clean[:, pool.data.shape[1]:]).any(1)
+    kinds["fail"] = np.nonzero((ok == 0) & (r == 0) & dirty)[0]
+    rs = sorted(set(r[r > 0].tolist()))
+    for rr in [rs[i] for i in _spread(0, len(rs) - 1, 3)]:
+        kinds[f"handoff{rr}"] = np.nonzero(r == rr)[0]
+    if ((r > 0) & (ok == 0)).any():
+        kinds["handoff_fail"] = np.nonzero((r > 0) & (ok == 0))[0]
+    # handoff_wide: the oracle corrects more symbols than the narrow run has indices, so the row's
+    # result rests on what the run on all slots does after the hand-off.  (Where a row that hands off
+    # is corrected within the narrow indices, no discrepancy follows the hand-off; where it is refused,
+    # it mostly is whatever became of the high coefficients.)
+    T = narrow_top(pool.parity.shape[1], gl)
+    if T is not None:
+        kinds["handoff_wide"] = np.nonzero((r > 0) & (ok == 1) & (want[1] > T))[0]
+    return {k: v for k, v in kinds.items() if len(v)}
+
+
+def group_layout(pool, want, gl):
+    """Batches in which the g = 64 // gl codewords of a wave, and the 256 // gl of a workgroup,
+    are alike or all but one: for every kind of general_kinds in turn a whole workgroup of it;
+    a workgroup of it with one codeword of the next kind at position 0, 1, half and the last;
+    a wave of it; a wave of it with one codeword of the next kind at group 0, 1, g / 2 and
+    g - 1.  (gl = 64: a wave is one codeword, and only the workgroups of four have a lone one.)
+    The workgroups come first, so each starts a workgroup of the kernel; every piece is whole
+    waves.  Returns the order and (name, start, length) of each piece."""
+    g, wg = WAVE // gl, GW_WORKGROUP // gl
+    kinds = general_kinds(pool, want, gl)
+    names = list(kinds)
+    out, pieces = [], []
+
+    def piece(name, rows):
+        pieces.append((name, sum(len(x) for x in out), len(rows)))
+        out.append(rows)
+
+    for width, label in ((wg, "workgroup"), (g, "wave")):
+        for n, a in enumerate(names):
+            piece(f"{label} of {a}", _fill(kinds[a], width, n))
+            b = names[(n + 1) % len(names)]
+            for k, at in enumerate(sorted({0, 1, width // 2, width - 1})):
+                if width == 1:
+                    continue
+                rows = _fill(kinds[a], width, n + k + 1)
+                rows[at] = kinds[b][k % len(kinds[b])]
+                piece(f"{label} of {a}, {b} at {at}", rows)
+    return np.concatenate(out), pieces
+
+
+def pair_stride(count, cus):
+    """The distance between the two codewords of a pass of rsgw_decode_k<., 64> (gw_grid: a
+    grid of min(ceil(count / 4), 8 CUs) workgroups of four codewords)"""
+    return min(-(-count // 4), 8 * cus) * 4
+
+
+def pair_layout(pool, want, cus, reps=3):
+    """A batch longer than one grid pass in which chosen codewords A and B share a wave
+    (gw_decode_pair: rows e and e + stride): clean / dirty and dirty / clean; fail / ok and
+    ok / fail; both at t errors; both clean; and where the code has a narrow run at GL 64,
+    hand-off at rA != rB in both orders, hand-off in A alone and in B alone, a failing
+    hand-off beside a correctable row and the reverse, and handoff_wide rows (general_kinds) as B
+    beside an A that never hands off or does so later, and the reverse.  Ordinary rows everywhere else; the count
+    is odd, so the last pass has rows without a partner.  Returns (order, stride, pairs), pairs:
+    (name, e) of each chosen pair."""
+    k = general_kinds(pool, want, 64)
+    t = pool.parity.shape[1] // 2
+    es = sorted(int(n[1:]) for n in k if n[0] == "e" and n[1:].isdigit())
+    k["dirty"] = np.concatenate([k[f"e{e}"] for e in es])
+    k["t"] = k[f"e{t}"]
+    combos = [("clean", "dirty"), ("dirty", "clean"), ("t", "t"), ("clean", "clean")]
+    if "fail" in k:  # (a code whose every dirty row the reference refuses has them under "dirty" too)
+        combos += [("fail", "dirty"), ("dirty", "fail"), ("fail", "fail")]
+    hs = sorted((int(n[7:]), n) for n in k if n.startswith("handoff") and n[7:].isdigit())
+    if hs:
+        quiet = np.array([r for r in k["dirty"] if pool.tags[r].handoff[64] == 0])
+        assert len(quiet), "every dirty row hands off"
+        k["quiet"] = quiet
+        first, last = hs[0][1], hs[-1][1]
+        combos += [(first, "quiet"), ("quiet", first), (last, "quiet"), ("quiet", last), (first, first)]
+        if len(hs) > 1:
+            combos += [(first, last), (last, first)]
+            if len(hs) > 2:
+                combos += [(hs[1][1], last), (first, hs[1][1])]
+        if "handoff_fail" in k:
+            combos += [("handoff_fail", "dirty"), ("dirty", "handoff_fail"), ("handoff_fail", last)]
+        if "handoff_wide" in k:  # B alone hands off, or hands off first, and its result shows it
+            combos += [("quiet", "handoff_wide"), ("handoff_wide", "quiet"), (last, "handoff_wide"), ("handoff_wide", last),
+                       ("clean", "handoff_wide"), ("handoff_wide", "handoff_wide")]
+    cap = pair_stride(1 << 30, cus)
+    npairs = len(combos) * reps
+    count = cap + npairs + 64 + (cap + npairs) % 2 + 1  # odd, and some filler rows have partners too
+    stride = pair_stride(count, cus)
+    assert stride == cap < count <= 2 * stride
+    filler = pool.where(lambda g: g.family == "ordinary")
+    order = _fill(filler, count)
+    pairs = []
+    for i, (a, b) in enumerate(combos * reps):
+        e = 5 * i % npairs if npairs % 5 else i  # (scattered over the slots of the workgroups)
+        order[e] = k[a][(i // len(combos)) % len(k[a])]
+        order[e + stride] = k[b][(i // len(combos) + 1) % len(k[b])]
+        pairs.append((f"{a} / {b}", e))
+    return order, stride, pairs
