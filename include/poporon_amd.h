@@ -782,6 +782,56 @@ bool poporon_cc_decode_device(const poporon_cc_t *cc, const int8_t *d_llr, size_
                               size_t count, int start_state, int end_state, uint8_t *d_bits, size_t bits_stride,
                               uint32_t *d_metric, void *stream);
 
+/* ---- K = 7 convolutional code: soft-output decode (max-log-MAP) ---------------
+ * The same code, puncturing, input LLRs, branch costs, blocks and windows as
+ * poporon_cc_decode_device; the output is one int8 LLR per info bit instead of a
+ * bit: the row that poporon_decode_soft_batch_device takes.  Integer arithmetic
+ * throughout, pinned here (tests/cc_soft_ref.py is the model).
+ *
+ * Window.  Block b owns the steps [bB, min(nbits, (b+1)B)) and runs the window
+ * [t0, t1) of the hard decode, n = t1 - t0 steps; blocks are independent.
+ * c_i(s, s') is the cost of step t0 + i on the branch from s to s' (the
+ * predecessors of s' are ((s' << 1) | d) & 63, the hypothesised input is
+ * s' >> 5).  "No path" is the number 2^28, added like any other cost: a window
+ * costs at most 6144 * 256, so nothing overflows 32 bits and every value below is
+ * defined.
+ *  - Forward: A_0(s) = 0 for all s; if t0 == 0 and start_state >= 0,
+ *    A_0(start_state) = 0 and A_0(s) = 2^28 for the other states.
+ *    A_{i+1}(s') = min over d of A_i(pred_d(s')) + c_i(pred_d(s'), s').
+ *  - Backward: Z_n(s) = 0 for all s; if t1 == nbits and end_state >= 0,
+ *    Z_n(end_state) = 0 and Z_n(s) = 2^28 for the other states.
+ *    Z_i(s) = min over the two successors s' of s of c_i(s, s') + Z_{i+1}(s').
+ *  - Output of an own step t = t0 + i: D_b = min over the s' with (s' >> 5) == b
+ *    of A_{i+1}(s') + Z_{i+1}(s'); x = D_1 - D_0 as a signed integer;
+ *    mag = min(127, |x| >> shift); d_soft[c*soft_stride + t] = x > 0 ? mag : -mag.
+ *    Negative means 1, as everywhere in the library; -128 is never written.
+ *
+ * Consequences (tests/test_cc_soft_cpu.py, tests/test_gpu_cc_soft.py):
+ *  - wherever the output is not 0 its sign bit is the bit that
+ *    poporon_cc_decode_device returns for the same handle, frame and boundary
+ *    states;
+ *  - min(D_0, D_1) of every own step of block b is that call's d_metric[b],
+ *    where end_state can be reached;
+ *  - with shift = 0 and nbits a multiple of 8 a frame's output is a valid d_llr
+ *    row of poporon_decode_soft_batch_device for m = 8: info bit t is bit
+ *    7 - t % 8 of byte t / 8 in both.
+ *
+ * shift is in [0, 8].  A frame writes exactly nbits bytes at d_soft +
+ * c*soft_stride; nothing between or around frames is written and d_llr is never
+ * written.  Any alignment, 64-bit offsets, asynchronous on `stream`, on the
+ * current HIP device.  The call fails before it touches the GPU, in this order,
+ * for a NULL handle, nbits == 0, a state outside -1..63, shift > 8, llr_stride <
+ * M, soft_stride < nbits and NULL d_llr or d_soft; count == 0 returns true
+ * without touching the GPU.  No host form, no kernel-timing id, no reserve call.
+ *
+ * How (cc_soft.hip): one wave per block, lane = state; the forward metrics are
+ * kept every 64 steps and computed again, 64 steps at a time, on the way back;
+ * count * blocks waves go out in launches of at most POPORON_AMD_CC_CHUNK blocks,
+ * as for the hard decode. */
+bool poporon_cc_decode_siso_device(const poporon_cc_t *cc, const int8_t *d_llr, size_t llr_stride, size_t nbits,
+                                   size_t count, int start_state, int end_state, unsigned shift, int8_t *d_soft,
+                                   size_t soft_stride, void *stream);
+
 /* ---- LDPC batches -----------------------------------------------------------
  * Row c has info_bytes (poporon_get_info_size) of data at d_data +
  * c*data_stride and parity_bytes (poporon_get_parity_size) of parity at

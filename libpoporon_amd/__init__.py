@@ -170,6 +170,8 @@ _SIGS = {
                                             _vp, _vp]),
     "poporon_cc_decode_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _vp,
                                             C.c_size_t, _vp, _vp]),
+    "poporon_cc_decode_siso_device": (C.c_bool, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
+                                                 C.c_uint, _vp, C.c_size_t, _vp]),
     "poporon_rng_create": (_vp, [C.c_int, _vp, C.c_size_t]),
     "poporon_rng_destroy": (None, [_vp]),
     "poporon_rng_next": (C.c_bool, [_vp, _vp, C.c_size_t]),
@@ -1277,6 +1279,14 @@ class Cc:
         self._check(self.lib.poporon_cc_decode_device(self.h, _dptr(d_llr), llr_stride, nbits, count, start_state,
                                                       end_state, _dptr(d_bits), bits_stride, _dptr(d_metric),
                                                       stream or None), "poporon_cc_decode_device")
+
+    def decode_soft(self, d_llr, llr_stride, nbits, count, d_soft, soft_stride, start_state=-1, end_state=-1, shift=0,
+                    stream=0):
+        """max-log-MAP: one int8 per info bit (negative = 1), |D_1 - D_0| >> shift saturated at 127; with shift 0 and
+        nbits a multiple of 8 a frame's row is an LLR row of Poporon.decode_soft_batch_device (m = 8)"""
+        self._check(self.lib.poporon_cc_decode_siso_device(self.h, _dptr(d_llr), llr_stride, nbits, count, start_state,
+                                                           end_state, shift, _dptr(d_soft), soft_stride,
+                                                           stream or None), "poporon_cc_decode_siso_device")
 
     def close(self):
         if getattr(self, "h", None):

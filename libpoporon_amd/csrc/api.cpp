@@ -4536,6 +4536,38 @@ EXPORT bool poporon_cc_decode_device(const poporon_cc_t *cc, const int8_t *d_llr
     return true;
 }
 
+EXPORT bool poporon_cc_decode_siso_device(const poporon_cc_t *cc, const int8_t *d_llr, size_t llr_stride, size_t nbits,
+                                          size_t count, int start_state, int end_state, unsigned shift, int8_t *d_soft,
+                                          size_t soft_stride, void *stream)
+{
+    const char *what = "poporon_cc_decode_siso_device";
+    if (!cc)
+        return fail("%s: NULL handle", what);
+    if (nbits == 0)
+        return fail("%s: nbits is 0", what);
+    if (start_state < -1 || start_state > 63)
+        return fail("%s: start_state %d outside [-1, 63]", what, start_state);
+    if (end_state < -1 || end_state > 63)
+        return fail("%s: end_state %d outside [-1, 63]", what, end_state);
+    if (shift > 8u)
+        return fail("%s: shift %u > 8", what, shift);
+    const size_t m = poporon_amd_cc_symbols(cc, nbits);
+    if (llr_stride < m)
+        return fail("%s: llr_stride %zu < the %zu symbols of a frame", what, llr_stride, m);
+    if (soft_stride < nbits)
+        return fail("%s: soft_stride %zu < the %zu bytes of a frame", what, soft_stride, nbits);
+    if (count == 0)
+        return true;
+    if (!d_llr || !d_soft)
+        return fail("%s: NULL argument", what);
+    const uint64_t blocks = poporon_amd_cc_blocks(cc, nbits), total = blocks * count;
+    for (uint64_t first = 0; first < total; first += cc->chunk)
+        HIP_OK(cck_decode_soft(&cc->p, d_llr, llr_stride, nbits, blocks, first,
+                               (uint32_t)std::min<uint64_t>(cc->chunk, total - first), start_state, end_state, shift,
+                               d_soft, soft_stride, static_cast<hipStream_t>(stream)));
+    return true;
+}
+
 /* ------------------------------------------------------------------------ */
 /* multi-GPU: one handle per device, contiguous codeword ranges             */
 /* ------------------------------------------------------------------------ */

@@ -42,21 +42,6 @@
  */
 #include "cc_device.h"
 
-#define CC_INF 0x10000000u /* a state no path reaches */
-
-static __device__ __forceinline__ uint32_t cc_label(const CcParams &p, uint32_t r)
-{
-    const uint32_t l0 = ((uint32_t)__popc(r & p.g0) ^ p.invert) & 1u;
-    const uint32_t l1 = ((uint32_t)__popc(r & p.g1) ^ (p.invert >> 1)) & 1u;
-    return l0 | l1 << 1;
-}
-
-static __device__ __forceinline__ uint32_t cc_prefix(const CcParams &p, uint32_t ph)
-{
-    const uint32_t below = (1u << ph) - 1u;
-    return (uint32_t)__popc(p.keep0 & below) + (uint32_t)__popc(p.keep1 & below);
-}
-
 __global__ __launch_bounds__(CC_STATES) void cc_decode_k(CcParams p, const int8_t *llr, size_t ls, uint64_t nbits,
                                                          uint64_t blocks, uint64_t first, int start_state,
                                                          int end_state, uint8_t *bits, size_t bs, uint32_t *metric_out)
